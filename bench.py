@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: train rays/s of the EmerNeRF hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 24 --warmup 6
+    python bench.py --gpus 1 --steps 24 --warmup 6 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,12 @@ proposal sampling -> field -> compositing -> losses -> backward -> (gradient exc
 of the flat gradient buffer, two of them hidden behind the backward) -> fused Adam.  Inputs (rays, parameters) are resident in HBM before the timed region.  Weak scaling:
 every rank draws its own 8192 rays; value = world * rays * steps / max-over-ranks(time).
 
-Prints ONE JSON line on rank 0 (fields per the driver contract + "roofline" + "cpu_baseline").
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step and what the same timed steps give for free: per-step spread, config).  --full adds
+everything that takes passes of its own after the timed region: the other launch mode, the instrumented per-kernel breakdown and
+the rooflines built on it, the CPU baseline with render parity, the lidar step and eval render, the trained-like and fp16-table
+states and the secondary configs (the --no-* options skip single parts of it).  --dump-outputs DIR writes what the timed
+path computes: the last timed step taken once more from the seeded parameters (dump_outputs).
 """
 import argparse
 import json
@@ -193,6 +198,50 @@ def rccl_summary(path, world):
     return {"world_size": world, "backend": "nccl (RCCL)", "log_lines_total": n, "log_excerpt": keep}
 
 
+DUMP_MAX_NUMEL = 1 << 20     # entries written per parameter tensor; larger tables are sampled
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(args, dev, world: int, batch: dict, step: int, out_dir: str, write: bool) -> None:
+    """What the timed path computes, as ``out_dir/<name>.npy`` (float32), reproducibly: the timed trainer's parameters after
+    init + warm-up + timed steps differ from run to run (the grid backward accumulates with float atomics, and Adam with eps 1e-15
+    turns last-bit differences of near-zero gradients into steps of lr, step after step), so the last timed step is taken once more
+    by a FRESH trainer -- same arguments and seed (hence the same initial parameters), same launch mode, the same batch and step
+    index as the last timed step -- and its results are written: the step's return value (``loss``, ``prop_grad`` as 0 / 1), the
+    gradients of the groups the step trains (``grad.model.<name>``, ``grad.prop<i>.<name>``) and every parameter of the model and
+    the proposal nets after its optimizer update (``model.<name>``, ``prop<i>.<name>``).  Every rank takes the step (it contains the
+    gradient exchange); rank 0 writes.  A tensor of more than DUMP_MAX_NUMEL entries is written as a fixed sample of DUMP_MAX_NUMEL
+    positions (a permutation seeded by its size, sorted), so two builds of the project write the same positions."""
+    import numpy as np
+    from emernerf_amd.trainer import Trainer
+    tr = Trainer(kind=args.kind, device=dev, num_samples=args.samples, world_size=world, table_init=args.table_init,
+                 use_graph=args.graph, table_dtype=args.table_dtype)
+    tr.set_step(step)
+    res = tr.train_step(batch)
+    torch.cuda.synchronize()
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = {"loss": res["loss"].detach().float().cpu().numpy(), "prop_grad": np.float32(1.0 if res["prop_grad"] else 0.0)}
+        trained = [("model", tr.model)] + ([(f"prop{len(tr.props) - 1}", tr.props[-1])] if res["prop_grad"] else [])
+        named = [("grad." + pre + "." + n, p.grad) for pre, m in trained for n, p in m.named_parameters()]
+        named += [("model." + n, p) for n, p in tr.model.named_parameters()]
+        named += [(f"prop{i}." + n, p) for i, m in enumerate(tr.props) for n, p in m.named_parameters()]
+        for name, t in named:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_MAX_NUMEL:
+                g = torch.Generator().manual_seed(flat.numel())
+                idx = torch.randperm(flat.numel(), generator=g)[:DUMP_MAX_NUMEL].sort().values
+                flat = flat[idx.to(flat.device)]
+                name += "@sample"
+            arrays[name] = flat.float().cpu().numpy()
+        total = sum(np.asarray(a).nbytes for a in arrays.values())
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total / 2**20:.1f} MB"
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+    del tr, res
+    torch.cuda.empty_cache()
+
+
 def measure_config(kind: str, rays: int, samples: int, dev, steps: int, warmup: int, init_steps: int, start_step: int = 1000,
                    use_graph: bool = False):
     """A short run of another BASELINE config on this GPU (rank 0, single GPU): ms/step, rays/s and the roofline of its xyzt
@@ -294,7 +343,14 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of BASELINE configs[2..4] (dynamic, flow, flow and feature at "
                     "the 2048-ray per-rank shard of configs[3])")
     ap.add_argument("--secondary-steps", type=int, default=0, help="timed steps of each secondary run (0: min(--steps, 12))")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every extra measurement (other launch mode, "
+                    "per-kernel breakdown and rooflines, CPU baseline, lidar step and eval render, trained-like and fp16-table states, "
+                    "secondary configs); a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computes from the seeded "
+                    "parameters (loss, gradients, updated parameters; large tables as a fixed sample) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC for RCCL; must be set before the HIP runtime starts
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,8 +438,8 @@ def main():
                               "emer_density_bwd_fused", "emer_rmlp_bwd_fused", "emer_composite_rgb_fwd", "emer_composite_rgb_bwd", "emer_reg_losses_fwd6",
                               "emer_reg_losses_bwd6", "emer_aggregate3_density_fwd", "emer_aggregate3_density_bwd", "emer_flow_warp_fwd", "emer_flow_warp_bwd"]
     # (graph replay launches no kernel from Python, so there is nothing to bracket inside the timed region: with --graph
-    # the roofline kernels are timed in the eager instrumented pass below instead)
-    timer = _lib.KernelTimer(grid_names) if (rank == 0 and not args.graph) else None
+    # the roofline kernels are timed in the eager instrumented pass below instead; without --full there is no roofline)
+    timer = _lib.KernelTimer(grid_names) if (rank == 0 and not args.graph and args.full) else None
     _lib.TIMER = timer
 
     if dp:
@@ -418,13 +474,15 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:   # the last timed step once more, from the seeded parameters (dump_outputs)
+        dump_outputs(args, dev, world, batches[(it["i"] - 1) % N_BATCHES], trainer.step_count - 1, args.dump_outputs, rank == 0)
 
     # the other launch mode over the same number of steps, so that the line shows both.  N > 1: every rank takes these steps (they
     # contain the collectives); a replayed step exchanges its gradients after the replay (one all-reduce of the main range, nothing
     # hidden), an eager step launches the hidden buckets from inside the backward -- which of the two wins at N ranks is what this
     # second figure is for.  Same bracket as the timed region: barrier + synchronize on both sides, MAX over ranks.
     other_mode = None
-    if True:
+    if args.full:
         was = trainer.use_graph
         trainer.use_graph = not was
         for _ in range(min(args.warmup, 6) + (8 if not was else 2)):   # (a first graph replay captures: warm it up)
@@ -455,21 +513,22 @@ def main():
     # untimed: per-kernel breakdown with every entry point instrumented.  EVERY rank takes these steps (a step contains the
     # gradient collectives: rank 0 alone would wait for its peers forever); only rank 0 records events.
     breakdown, breakdown_steps = None, min(args.steps, 12)
-    if rank == 0:
-        breakdown = _lib.KernelTimer(all_names)
-        _lib.TIMER = breakdown
-    graphed, trainer.use_graph = trainer.use_graph, False  # the instrumented pass launches eagerly
-    for _ in range(breakdown_steps):
-        trainer.train_step(next_batch())
-    torch.cuda.synchronize()
-    trainer.use_graph = graphed
-    _lib.TIMER = None
-    if rank == 0 and timer is None:
-        timer = breakdown
+    if args.full:
+        if rank == 0:
+            breakdown = _lib.KernelTimer(all_names)
+            _lib.TIMER = breakdown
+        graphed, trainer.use_graph = trainer.use_graph, False  # the instrumented pass launches eagerly
+        for _ in range(breakdown_steps):
+            trainer.train_step(next_batch())
+        torch.cuda.synchronize()
+        trainer.use_graph = graphed
+        _lib.TIMER = None
+        if rank == 0 and timer is None:
+            timer = breakdown
     # CPU baseline + render parity (PSNR / depth error of the HIP path vs the oracle on the same parameters), evaluated
     # on the state the timed region left -- before the extra measurements below train the model further
     cpu_res = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu_res = cpu_baseline(trainer, args.cpu_rays, args.samples)
         except Exception as e:  # the baseline is reporting only; never lose the GPU number over it
@@ -478,7 +537,7 @@ def main():
     # the lidar optimizer step of a reference iteration (train_emernerf.py:747-826) and the evaluation render loop
     # (video_utils.py:50-468: eval mode, return_decomposition, 16 384-ray chunks, results copied to the host).
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extras:  # single-GPU measurements (the lidar step contains the collectives)
+    if args.full and rank == 0 and world == 1 and not args.no_extras:  # single-GPU measurements (the lidar step contains the collectives)
         from emernerf_amd.trainer import synthetic_lidar_rays
         lidar = [synthetic_lidar_rays(args.rays, dev, seed=2000 + i) for i in range(4)]
         for i in range(8):
@@ -506,7 +565,7 @@ def main():
     # magnitude along a ray, so the proposal sampler clusters the 128 samples -- the distribution the owner-computes
     # backward is sensitive to.  Same model, same rays, grid kernels timed with HIP events over 12 steps.
     clustered = None
-    if rank == 0 and args.table_init is None and not args.no_second_state:
+    if args.full and rank == 0 and args.table_init is None and not args.no_second_state:
         t2 = Trainer(kind=args.kind, device=dev, num_samples=args.samples, world_size=1, table_init=0.3)
         t2.set_step(args.start_step)
         for _ in range(18):
@@ -534,7 +593,7 @@ def main():
     # BASELINE configs[1] names fp16 tables; the headline runs the reference's fp32.  A third short run with half-precision tables
     # (fp32 master cast per call, fp32 gradient accumulation) reports the grid pair of THAT mode next to it.
     fp16_state = None
-    if rank == 0 and world == 1 and args.table_dtype == "f32" and args.kind == "static" and not args.no_fp16_state:
+    if args.full and rank == 0 and world == 1 and args.table_dtype == "f32" and args.kind == "static" and not args.no_fp16_state:
         t3 = Trainer(kind=args.kind, device=dev, num_samples=args.samples, world_size=1, table_dtype="f16")
         t3.set_step(args.start_step)
         for _ in range(18):
@@ -554,7 +613,7 @@ def main():
     # that the driver's line carries them): dynamic and flow at 8192 x 128, and flow at 2048 x 128 -- the per-rank shard of
     # configs[3] ("16384 rays over 8 GPUs")
     secondary = None
-    if rank == 0 and world == 1 and args.kind == "static" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.kind == "static" and not args.no_secondary:
         ss = args.secondary_steps or min(args.steps, 12)
         secondary = []
         # ... and configs[4] (flow + feature head) at its 2048-ray shard
@@ -570,82 +629,7 @@ def main():
         N = args.rays * args.samples
         c = trainer.cfg.xyz_encoder
         D, L, F = c.n_input_dims, c.n_levels, c.n_features_per_level
-        us = timer.elapsed_us()
-        tags = timer.tags
-
-        def main_grid(name):  # launches on the main (L-level, F-feature) grid only, not the proposal grids
-            return [u for u, tg in zip(us[name], tags[name]) if tg == (D, L, F)]
-
-        fwd_b, bwd_b = grid_alg_bytes(D, L, F)
-        f_us, b_us = main_grid("emer_hashgrid_fwd"), main_grid("emer_hashgrid_bwd_params_sliced")
-        # data-parallel eager steps run the table's backward as two level-range launches (the first range's all-reduce starts
-        # between them): one backward = the sum of a pair
-        lv = main_grid("emer_hashgrid_bwd_params_sliced_levels")
-        b_us = b_us + [lv[i] + lv[i + 1] for i in range(0, len(lv) - 1, 2)]
-        f_avg = sum(f_us) / max(len(f_us), 1)
-        b_avg = sum(b_us) / max(len(b_us), 1)
-
-        def spread(v):   # median and the 10th / 90th percentile of the per-launch durations next to the average the roofline uses
-            s_ = sorted(v)
-            return {"median": s_[len(s_) // 2], "p10": s_[len(s_) // 10], "p90": s_[(9 * len(s_)) // 10], "launches": len(s_)} if s_ else None
-        per_kernel = {n: {"launches_per_step": len(v) / breakdown_steps, "ms_per_step": sum(v) / 1e3 / breakdown_steps,
-                          "avg_us": (sum(v) / len(v)) if v else 0.0}
-                      for n, v in breakdown.elapsed_us().items() if v}
-        dominant = "emer_hashgrid_bwd_params_sliced" if b_avg >= f_avg else "emer_hashgrid_fwd"
-        dom_us, dom_bytes = (b_avg, bwd_b * N) if dominant.endswith("sliced") else (f_avg, fwd_b * N)
-        ach = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
-        both = (fwd_b + bwd_b) * N / ((f_avg + b_avg) * 1e-6) / 1e9 if (f_avg + b_avg) > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(dominant, D, F, args)
-        # [r6] the proposal networks' grids (L8/F1/T2^20, default_config.yaml:51-58): two forward launches per step (8192 x 128 and
-        # 8192 x 64 samples on the SAME table -- the reference's late-binding lambda), backward + in-kernel add on one step in six
-        pk = PROP_SHAPE
-        roof_prop = grid_roofline(timer, pk, args.steps)
-        if roof_prop is not None:
-            roof_prop["grid"] += "/T2^20 (proposal nets; both rounds query the last one)"
-            roof_prop["timed_in"] = "the same event-bracketed loop as `roofline`"
         step_traffic = pmc_step_traffic(args)
-        roof2 = None
-        if clustered is not None:
-            us2, tg2 = clustered.elapsed_us(), clustered.tags
-            f2 = [u for u, tg in zip(us2["emer_hashgrid_fwd"], tg2["emer_hashgrid_fwd"]) if tg == (D, L, F)]
-            b2 = [u for u, tg in zip(us2["emer_hashgrid_bwd_params_sliced"], tg2["emer_hashgrid_bwd_params_sliced"]) if tg == (D, L, F)]
-            if f2 and b2:
-                fa, ba = sum(f2) / len(f2), sum(b2) / len(b2)
-                roof2 = {"table_init": 0.3, "ms_per_step": clustered_ms, "bound": "hbm", "kernel": "emer_hashgrid_bwd_params_sliced", "avg_us": ba,
-                         "achieved": bwd_b * N / (ba * 1e-6) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": bwd_b * N / (ba * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-                         "grid_encode_plus_bwd": {"fwd_avg_us": fa, "bwd_avg_us": ba,
-                                                  "frac": (fwd_b + bwd_b) * N / ((fa + ba) * 1e-6) / 1e9 / HBM_PEAK_GBPS}}
-        roof16 = None
-        if fp16_state is not None:
-            us3, tg3 = fp16_state["timer"].elapsed_us(), fp16_state["timer"].tags
-            f3 = [u for u, tg in zip(us3["emer_hashgrid_fwd"], tg3["emer_hashgrid_fwd"]) if tg == (D, L, F)]
-            b3 = [u for u, tg in zip(us3["emer_hashgrid_bwd_params_sliced"], tg3["emer_hashgrid_bwd_params_sliced"]) if tg == (D, L, F)]
-            if f3 and b3:
-                fa3, ba3 = sum(f3) / len(f3), sum(b3) / len(b3)
-                fwd16, bwd16 = grid_alg_bytes(D, L, F, sp=2, so=4, sg=4)   # fp16 gathers, fp32 encodings and gradient accumulation
-                roof16 = {"tables": "fp16 copy of the fp32 master per call (emer_cast_f32_f16), fp32 encodings, fp32 gradient accumulation "
-                                    "(owner-computes backward, never reads the table)", "bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                          "fwd_avg_us": fa3, "bwd_avg_us": ba3, "algorithmic_bytes_per_sample": {"fwd": fwd16, "bwd": bwd16},
-                          "frac_encode_plus_bwd": (fwd16 + bwd16) * N / ((fa3 + ba3) * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-                          "baseline_md_target_us": 711, "pair_us": fa3 + ba3, "ms_per_step": fp16_state["ms_per_step"],
-                          "note": "BASELINE.md 2.3 counts 2712 B/sample for this mode (fp16 encodings: 588 + 2124); this path keeps the "
-                                  "encodings fp32 (the fused heads consume fp32): 652 + 2188 B"}
-        # xyzt grids of the dynamic / flow configs (dynamic and flow encoders share one shape): their own roofline block
-        roof_xyzt = None
-        dyn = getattr(trainer.cfg, "dynamic_xyz_encoder", None)
-        if args.kind != "static" and dyn is not None:
-            D4, L4, F4 = dyn.n_input_dims, dyn.n_levels, dyn.n_features_per_level
-            f4 = [u for u, tg in zip(us["emer_hashgrid_fwd"], tags["emer_hashgrid_fwd"]) if tg == (D4, L4, F4)]
-            b4 = [u for k4 in ("emer_hashgrid_bwd_params_sliced", "emer_hashgrid_bwd_params_sliced_add") for u, tg in zip(us[k4], tags[k4]) if tg == (D4, L4, F4)]
-            if f4 and b4:
-                fb4, bb4 = grid_alg_bytes(D4, L4, F4)
-                fa4, ba4 = sum(f4) / len(f4), sum(b4) / len(b4)
-                roof_xyzt = {"grid": f"D{D4}/L{L4}/F{F4}/T2^{dyn.log2_hashmap_size} (dynamic and flow encoders)", "bound": "hbm",
-                             "launches_per_step": {"fwd": len(f4) / args.steps, "bwd": len(b4) / args.steps},
-                             "fwd_avg_us": fa4, "bwd_avg_us": ba4, "algorithmic_bytes_per_sample": {"fwd": fb4, "bwd": bb4},
-                             "frac_bwd": bb4 * N / (ba4 * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-                             "frac_encode_plus_bwd": (fb4 + bb4) * N / ((fa4 + ba4) * 1e-6) / 1e9 / HBM_PEAK_GBPS, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
         workloads = {
             "static": "BASELINE.json configs[1]: static-only RadianceField",
             "dynamic": "BASELINE.json configs[2] (default_dynamic.yaml): static + dynamic xyzt grid D4/L10/F4/T2^18 + shadow head",
@@ -653,47 +637,123 @@ def main():
                     "(8192 rays per GPU; the config names 16384 rays over 8 GPUs)",
             "feature": "BASELINE.json configs[4]: flow model + feature head (E=64) + learnable PE, 3 cameras (8192 rays per GPU)",
         }
-        # Matrix-pipe rooflines of the head kernels (static configuration only: hidden 64, geo 64).  `achieved` = algorithmic
-        # (fp32-equivalent) flops of one launch / its average duration in the instrumented pass; the kernels execute SIX
-        # bf16 partial products per fp32 product (exact 3-term splits, csrc/mlp_fused.hip), so the bf16 pipe does 6x that, plus -- in the
-        # fused backward kernels -- the transposer passes that put rows on the reduction index (3 instructions of 16 x 16 x 32 per
-        # 16 x 16 operand tile = 3072 flops per row and tile).  [r4] their weight gradients run on v_mfma_f32_32x32x16_bf16 (full K);
-        # `executed` = all of that, `frac` = executed / 2.5 PFLOP/s dense bf16.
-        mfma = {}
-        if args.kind == "static":
-            k0 = L * F
-            n_out = trainer.model.base_mlp[2].out_features
-            dgrad_neck, wgrad_neck = 2.0 * N * (64 * 64 + 64 * k0), 2.0 * N * (64 * n_out + 64 * k0)
-            # (no "emer_neck_fwd" entry: in the static step the main neck runs inside emer_field_fwd, and the emer_neck_fwd launches
-            # that remain are the proposal nets' 8 -> 64 -> 1 density MLPs on exact-fp32 matrix instructions)
-            flops = {"emer_neck_bwd": (dgrad_neck, 6.0),
-                     "emer_neck_bwd_fused": (dgrad_neck + wgrad_neck, None),
-                     "emer_rgb_head_fwd": (2.0 * N * (64 * 64 + 128 * 64 + 64 * 3), 6.0),
-                     "emer_field_fwd": (2.0 * N * (k0 * 64 + 64 * 64) + 2.0 * N * (64 * 64 + 128 * 64 + 64 * 3), 6.0),  # neck + rgb head in one launch
-                     "emer_rgb_head_bwd": (2.0 * N * (3 * 64 + 3 * 64 * 64), 6.0),
-                     # [r4] data gradients + the weight gradients of the per-sample column blocks (dW1 [64][128], dW0 [64][64]); the transposer
-                     # handles dpre1 / dpre0 only (8 tiles per 16 rows: a1 / geo are read transposed from LDS)
-                     "emer_rgb_head_bwd_fused": (2.0 * N * (3 * 64 + 3 * 64 * 64) + 2.0 * N * (64 * 128 + 64 * 64), None),
-                     # [r6] the same + the recomputation of a1 / a2 (3 x 64 x 64 MACs per sample); the transposer handles dpre1 / dpre0 / a1 / geo
-                     "emer_rgb_head_bwd_recompute": (2.0 * N * (3 * 64 + 3 * 64 * 64) + 2.0 * N * (64 * 128 + 64 * 64) + 2.0 * N * 3 * 64 * 64, None)}
-            for kn, (fl, mult) in flops.items():
-                v = [u for u in breakdown.elapsed_us().get(kn, [])]
-                if kn.startswith("emer_neck"):  # main-field launches only (the proposal nets are the short ones; in the static step the forward runs inside emer_field_fwd)
-                    v = sorted(v)[-max(1, breakdown_steps):]
-                if v:
-                    t = sum(v) / len(v)
-                    t_row = 3.0 * 2.0 * 16 * 32        # transposer flops per row and 16 x 16 operand tile
-                    if kn == "emer_rgb_head_bwd_fused":
-                        ex = 6.0 * fl + t_row * 8 * N
-                    elif kn == "emer_rgb_head_bwd_recompute":
-                        ex = 6.0 * fl + t_row * 16 * N
-                    elif kn == "emer_neck_bwd_fused":    # tiles: h1 (4), d (4), dpre0 (4), the encoding ((k0 + 15) // 16)
-                        ex = 6.0 * fl + t_row * (12 + (k0 + 15) // 16) * N
-                    else:
-                        ex = fl * mult
-                    mfma[kn] = {"avg_us": t, "achieved": fl / (t * 1e-6) / 1e12, "executed": ex / (t * 1e-6) / 1e12, "peak": BF16_MFMA_PEAK_TFLOPS,
-                                "unit": "TFLOP/s", "frac": ex / (t * 1e-6) / 1e12 / BF16_MFMA_PEAK_TFLOPS,
-                                "vs_fp32_matrix_peak": fl / (t * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS}
+        if args.full:   # the figures built on the passes after the timed region
+            us = timer.elapsed_us()
+            tags = timer.tags
+
+            def main_grid(name):  # launches on the main (L-level, F-feature) grid only, not the proposal grids
+                return [u for u, tg in zip(us[name], tags[name]) if tg == (D, L, F)]
+
+            fwd_b, bwd_b = grid_alg_bytes(D, L, F)
+            f_us, b_us = main_grid("emer_hashgrid_fwd"), main_grid("emer_hashgrid_bwd_params_sliced")
+            # data-parallel eager steps run the table's backward as two level-range launches (the first range's all-reduce starts
+            # between them): one backward = the sum of a pair
+            lv = main_grid("emer_hashgrid_bwd_params_sliced_levels")
+            b_us = b_us + [lv[i] + lv[i + 1] for i in range(0, len(lv) - 1, 2)]
+            f_avg = sum(f_us) / max(len(f_us), 1)
+            b_avg = sum(b_us) / max(len(b_us), 1)
+
+            def spread(v):   # median and the 10th / 90th percentile of the per-launch durations next to the average the roofline uses
+                s_ = sorted(v)
+                return {"median": s_[len(s_) // 2], "p10": s_[len(s_) // 10], "p90": s_[(9 * len(s_)) // 10], "launches": len(s_)} if s_ else None
+            per_kernel = {n: {"launches_per_step": len(v) / breakdown_steps, "ms_per_step": sum(v) / 1e3 / breakdown_steps,
+                              "avg_us": (sum(v) / len(v)) if v else 0.0}
+                          for n, v in breakdown.elapsed_us().items() if v}
+            dominant = "emer_hashgrid_bwd_params_sliced" if b_avg >= f_avg else "emer_hashgrid_fwd"
+            dom_us, dom_bytes = (b_avg, bwd_b * N) if dominant.endswith("sliced") else (f_avg, fwd_b * N)
+            ach = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
+            both = (fwd_b + bwd_b) * N / ((f_avg + b_avg) * 1e-6) / 1e9 if (f_avg + b_avg) > 0 else 0.0
+            traffic, traffic_src = pmc_traffic(dominant, D, F, args)
+            # [r6] the proposal networks' grids (L8/F1/T2^20, default_config.yaml:51-58): two forward launches per step (8192 x 128 and
+            # 8192 x 64 samples on the SAME table -- the reference's late-binding lambda), backward + in-kernel add on one step in six
+            pk = PROP_SHAPE
+            roof_prop = grid_roofline(timer, pk, args.steps)
+            if roof_prop is not None:
+                roof_prop["grid"] += "/T2^20 (proposal nets; both rounds query the last one)"
+                roof_prop["timed_in"] = "the same event-bracketed loop as `roofline`"
+            roof2 = None
+            if clustered is not None:
+                us2, tg2 = clustered.elapsed_us(), clustered.tags
+                f2 = [u for u, tg in zip(us2["emer_hashgrid_fwd"], tg2["emer_hashgrid_fwd"]) if tg == (D, L, F)]
+                b2 = [u for u, tg in zip(us2["emer_hashgrid_bwd_params_sliced"], tg2["emer_hashgrid_bwd_params_sliced"]) if tg == (D, L, F)]
+                if f2 and b2:
+                    fa, ba = sum(f2) / len(f2), sum(b2) / len(b2)
+                    roof2 = {"table_init": 0.3, "ms_per_step": clustered_ms, "bound": "hbm", "kernel": "emer_hashgrid_bwd_params_sliced", "avg_us": ba,
+                             "achieved": bwd_b * N / (ba * 1e-6) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": bwd_b * N / (ba * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                             "grid_encode_plus_bwd": {"fwd_avg_us": fa, "bwd_avg_us": ba,
+                                                      "frac": (fwd_b + bwd_b) * N / ((fa + ba) * 1e-6) / 1e9 / HBM_PEAK_GBPS}}
+            roof16 = None
+            if fp16_state is not None:
+                us3, tg3 = fp16_state["timer"].elapsed_us(), fp16_state["timer"].tags
+                f3 = [u for u, tg in zip(us3["emer_hashgrid_fwd"], tg3["emer_hashgrid_fwd"]) if tg == (D, L, F)]
+                b3 = [u for u, tg in zip(us3["emer_hashgrid_bwd_params_sliced"], tg3["emer_hashgrid_bwd_params_sliced"]) if tg == (D, L, F)]
+                if f3 and b3:
+                    fa3, ba3 = sum(f3) / len(f3), sum(b3) / len(b3)
+                    fwd16, bwd16 = grid_alg_bytes(D, L, F, sp=2, so=4, sg=4)   # fp16 gathers, fp32 encodings and gradient accumulation
+                    roof16 = {"tables": "fp16 copy of the fp32 master per call (emer_cast_f32_f16), fp32 encodings, fp32 gradient accumulation "
+                                        "(owner-computes backward, never reads the table)", "bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                              "fwd_avg_us": fa3, "bwd_avg_us": ba3, "algorithmic_bytes_per_sample": {"fwd": fwd16, "bwd": bwd16},
+                              "frac_encode_plus_bwd": (fwd16 + bwd16) * N / ((fa3 + ba3) * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                              "baseline_md_target_us": 711, "pair_us": fa3 + ba3, "ms_per_step": fp16_state["ms_per_step"],
+                              "note": "BASELINE.md 2.3 counts 2712 B/sample for this mode (fp16 encodings: 588 + 2124); this path keeps the "
+                                      "encodings fp32 (the fused heads consume fp32): 652 + 2188 B"}
+            # xyzt grids of the dynamic / flow configs (dynamic and flow encoders share one shape): their own roofline block
+            roof_xyzt = None
+            dyn = getattr(trainer.cfg, "dynamic_xyz_encoder", None)
+            if args.kind != "static" and dyn is not None:
+                D4, L4, F4 = dyn.n_input_dims, dyn.n_levels, dyn.n_features_per_level
+                f4 = [u for u, tg in zip(us["emer_hashgrid_fwd"], tags["emer_hashgrid_fwd"]) if tg == (D4, L4, F4)]
+                b4 = [u for k4 in ("emer_hashgrid_bwd_params_sliced", "emer_hashgrid_bwd_params_sliced_add") for u, tg in zip(us[k4], tags[k4]) if tg == (D4, L4, F4)]
+                if f4 and b4:
+                    fb4, bb4 = grid_alg_bytes(D4, L4, F4)
+                    fa4, ba4 = sum(f4) / len(f4), sum(b4) / len(b4)
+                    roof_xyzt = {"grid": f"D{D4}/L{L4}/F{F4}/T2^{dyn.log2_hashmap_size} (dynamic and flow encoders)", "bound": "hbm",
+                                 "launches_per_step": {"fwd": len(f4) / args.steps, "bwd": len(b4) / args.steps},
+                                 "fwd_avg_us": fa4, "bwd_avg_us": ba4, "algorithmic_bytes_per_sample": {"fwd": fb4, "bwd": bb4},
+                                 "frac_bwd": bb4 * N / (ba4 * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                                 "frac_encode_plus_bwd": (fb4 + bb4) * N / ((fa4 + ba4) * 1e-6) / 1e9 / HBM_PEAK_GBPS, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
+            # Matrix-pipe rooflines of the head kernels (static configuration only: hidden 64, geo 64).  `achieved` = algorithmic
+            # (fp32-equivalent) flops of one launch / its average duration in the instrumented pass; the kernels execute SIX
+            # bf16 partial products per fp32 product (exact 3-term splits, csrc/mlp_fused.hip), so the bf16 pipe does 6x that, plus -- in the
+            # fused backward kernels -- the transposer passes that put rows on the reduction index (3 instructions of 16 x 16 x 32 per
+            # 16 x 16 operand tile = 3072 flops per row and tile).  [r4] their weight gradients run on v_mfma_f32_32x32x16_bf16 (full K);
+            # `executed` = all of that, `frac` = executed / 2.5 PFLOP/s dense bf16.
+            mfma = {}
+            if args.kind == "static":
+                k0 = L * F
+                n_out = trainer.model.base_mlp[2].out_features
+                dgrad_neck, wgrad_neck = 2.0 * N * (64 * 64 + 64 * k0), 2.0 * N * (64 * n_out + 64 * k0)
+                # (no "emer_neck_fwd" entry: in the static step the main neck runs inside emer_field_fwd, and the emer_neck_fwd launches
+                # that remain are the proposal nets' 8 -> 64 -> 1 density MLPs on exact-fp32 matrix instructions)
+                flops = {"emer_neck_bwd": (dgrad_neck, 6.0),
+                         "emer_neck_bwd_fused": (dgrad_neck + wgrad_neck, None),
+                         "emer_rgb_head_fwd": (2.0 * N * (64 * 64 + 128 * 64 + 64 * 3), 6.0),
+                         "emer_field_fwd": (2.0 * N * (k0 * 64 + 64 * 64) + 2.0 * N * (64 * 64 + 128 * 64 + 64 * 3), 6.0),  # neck + rgb head in one launch
+                         "emer_rgb_head_bwd": (2.0 * N * (3 * 64 + 3 * 64 * 64), 6.0),
+                         # [r4] data gradients + the weight gradients of the per-sample column blocks (dW1 [64][128], dW0 [64][64]); the transposer
+                         # handles dpre1 / dpre0 only (8 tiles per 16 rows: a1 / geo are read transposed from LDS)
+                         "emer_rgb_head_bwd_fused": (2.0 * N * (3 * 64 + 3 * 64 * 64) + 2.0 * N * (64 * 128 + 64 * 64), None),
+                         # [r6] the same + the recomputation of a1 / a2 (3 x 64 x 64 MACs per sample); the transposer handles dpre1 / dpre0 / a1 / geo
+                         "emer_rgb_head_bwd_recompute": (2.0 * N * (3 * 64 + 3 * 64 * 64) + 2.0 * N * (64 * 128 + 64 * 64) + 2.0 * N * 3 * 64 * 64, None)}
+                for kn, (fl, mult) in flops.items():
+                    v = [u for u in breakdown.elapsed_us().get(kn, [])]
+                    if kn.startswith("emer_neck"):  # main-field launches only (the proposal nets are the short ones; in the static step the forward runs inside emer_field_fwd)
+                        v = sorted(v)[-max(1, breakdown_steps):]
+                    if v:
+                        t = sum(v) / len(v)
+                        t_row = 3.0 * 2.0 * 16 * 32        # transposer flops per row and 16 x 16 operand tile
+                        if kn == "emer_rgb_head_bwd_fused":
+                            ex = 6.0 * fl + t_row * 8 * N
+                        elif kn == "emer_rgb_head_bwd_recompute":
+                            ex = 6.0 * fl + t_row * 16 * N
+                        elif kn == "emer_neck_bwd_fused":    # tiles: h1 (4), d (4), dpre0 (4), the encoding ((k0 + 15) // 16)
+                            ex = 6.0 * fl + t_row * (12 + (k0 + 15) // 16) * N
+                        else:
+                            ex = fl * mult
+                        mfma[kn] = {"avg_us": t, "achieved": fl / (t * 1e-6) / 1e12, "executed": ex / (t * 1e-6) / 1e12, "peak": BF16_MFMA_PEAK_TFLOPS,
+                                    "unit": "TFLOP/s", "frac": ex / (t * 1e-6) / 1e12 / BF16_MFMA_PEAK_TFLOPS,
+                                    "vs_fp32_matrix_peak": fl / (t * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS}
         out = {
             "metric": "train rays/sec (8192-ray batch, 128 samples)",
             "value": world * args.rays * args.steps / elapsed,
@@ -728,26 +788,29 @@ def main():
                        "table_init": args.table_init if args.table_init is not None else "tcnn +-1e-4", "table_dtype": args.table_dtype,
                        "launch_mode": "hipGraph replay of forward+backward (exchange + Adam eager)" if args.graph else "eager",
                        "other_launch_mode": other_mode},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src, "avg_us": dom_us, "algorithmic_bytes_per_launch": dom_bytes,
-                         "timed_in": (f"HIP events on the dispatch packets of the eager loop of {args.steps} steps that follows the hipGraph-timed "
-                                      "region (config.other_launch_mode; a graph replay launches nothing from the host to bracket)")
-                         if (args.graph and world == 1) else "HIP events on the dispatch packets inside the timed region",
-                         "grid_encode_plus_bwd": {"achieved": both, "frac": both / HBM_PEAK_GBPS, "fwd_avg_us": f_avg, "fwd_us_spread": spread(f_us), "bwd_us_spread": spread(b_us),
-                                                  "bwd_avg_us": b_avg, "algorithmic_bytes": (fwd_b + bwd_b) * N}},
-            "roofline_prop": roof_prop,
-            "roofline_trained_like": roof2,
-            "roofline_fp16_tables": roof16,
-            "roofline_xyzt": roof_xyzt,
-            "lidar_step": extra.get("lidar_step"),
-            "eval_render": extra.get("eval_render"),
-            "roofline_mfma": mfma,
-            "secondary": secondary,
             "source_sha16": source_hash(),
-            "kernels": per_kernel,
-            "kernels_note": f"per-kernel breakdown from a separate fully instrumented pass of {breakdown_steps} steps after the "
-                            "timed region; the roofline kernels are timed with HIP events inside the timed region itself",
         }
+        if args.full:
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": ach / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src, "avg_us": dom_us, "algorithmic_bytes_per_launch": dom_bytes,
+                             "timed_in": (f"HIP events on the dispatch packets of the eager loop of {args.steps} steps that follows the hipGraph-timed "
+                                          "region (config.other_launch_mode; a graph replay launches nothing from the host to bracket)")
+                             if (args.graph and world == 1) else "HIP events on the dispatch packets inside the timed region",
+                             "grid_encode_plus_bwd": {"achieved": both, "frac": both / HBM_PEAK_GBPS, "fwd_avg_us": f_avg, "fwd_us_spread": spread(f_us), "bwd_us_spread": spread(b_us),
+                                                      "bwd_avg_us": b_avg, "algorithmic_bytes": (fwd_b + bwd_b) * N}},
+                "roofline_prop": roof_prop,
+                "roofline_trained_like": roof2,
+                "roofline_fp16_tables": roof16,
+                "roofline_xyzt": roof_xyzt,
+                "lidar_step": extra.get("lidar_step"),
+                "eval_render": extra.get("eval_render"),
+                "roofline_mfma": mfma,
+                "secondary": secondary,
+                "kernels": per_kernel,
+                "kernels_note": f"per-kernel breakdown from a separate fully instrumented pass of {breakdown_steps} steps after the "
+                                "timed region; the roofline kernels are timed with HIP events inside the timed region itself",
+            })
         if dp:
             out["rccl"] = rccl_summary(os.environ.get("NCCL_DEBUG_FILE", rccl_log), world)
             out["rccl"].update({"env": {k: os.environ[k] for k in ("NCCL_ALGO", "NCCL_PROTO", "EMER_DP_MODE", "NCCL_MIN_NCHANNELS") if k in os.environ}})

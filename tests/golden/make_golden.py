@@ -1,6 +1,7 @@
 """Generate golden vectors by running the REFERENCE's own Python on CPU (build container only).
 
-    python tests/golden/make_golden.py            # writes tests/golden/*.npz
+    python tests/golden/make_golden.py            # writes tests/golden/*.npz and import_swaps.json
+    python tests/golden/make_golden.py import_swaps    # one fixture by name
 
 /root/reference's radiance_fields / render_utils / nerfacc_prop_net are imported UNMODIFIED on top of the
 import shims of oracle/ref_shims.py (CPU oracle standing in for the absent tcnn / nerfacc binaries).  Each
@@ -537,6 +538,82 @@ def run_lidar_source_case(seed: int = 1300, n_steps: int = 6, n_train: int = 80)
     return out
 
 
+# the reference's OWN construction code on the four import swaps, installed the way Python resolves them
+# (``sys.modules`` entries for ``third_party.tcnn_modules`` -> ``emernerf_amd.tcnn_modules`` and ``nerfacc`` (+ ``.data_specs``,
+# ``.estimators.base``, ``.pdf``, ``.volrend``) -> ``emernerf_amd.nerfacc_compat``).  Runs in a subprocess (the reference's top-level
+# packages must not leak into this process) and prints one JSON record: per model kind and proposal net the state_dict keys, shapes,
+# dtypes and a sha256 of every tensor's bytes (same seed, same construction order), and the proposal schedule.
+IMPORT_SWAPS_SCRIPT = '''
+import hashlib, json, sys, types
+sys.path.insert(0, %(root)r)
+sys.path.insert(0, %(ref)r)
+import torch
+import emernerf_amd.tcnn_modules as amd_tcnn
+import emernerf_amd.nerfacc_compat as NC
+import third_party                                   # the reference's (empty-__init__) package
+sys.modules["third_party.tcnn_modules"] = amd_tcnn   # encodings.py:9
+third_party.tcnn_modules = amd_tcnn
+nerfacc = types.ModuleType("nerfacc")
+for name in ("accumulate_along_rays", "render_transmittance_from_density", "render_weight_from_density"):
+    setattr(nerfacc, name, getattr(NC, name))        # render_utils.py:4-8, loss/base.py:7
+def sub(name, **attrs):
+    m = types.ModuleType(name)
+    for k, v in attrs.items():
+        setattr(m, k, v)
+    sys.modules[name] = m
+    return m
+sys.modules["nerfacc"] = nerfacc
+nerfacc.data_specs = sub("nerfacc.data_specs", RayIntervals=NC.RayIntervals)                       # nerfacc_prop_net.py:11
+nerfacc.estimators = sub("nerfacc.estimators")
+nerfacc.estimators.base = sub("nerfacc.estimators.base", AbstractEstimator=NC.AbstractEstimator)   # :12
+nerfacc.pdf = sub("nerfacc.pdf", importance_sampling=NC.importance_sampling, searchsorted=NC.searchsorted)   # :13
+nerfacc.volrend = sub("nerfacc.volrend", render_transmittance_from_density=NC.render_transmittance_from_density)  # :14
+sub("omegaconf", OmegaConf=type("OmegaConf", (), {}))   # not a swap: type annotations only on this path
+
+from radiance_fields.radiance_field import build_radiance_field_from_cfg as ref_build, build_density_field as ref_density
+from radiance_fields import render_utils as ref_render_utils
+from third_party.nerfacc_prop_net import PropNetEstimator as RefEstimator, get_proposal_requires_grad_fn
+import loss.base as ref_loss
+import radiance_fields.encodings as ref_enc
+assert ref_enc.tcnn is amd_tcnn, "encodings.py must have bound the swapped tcnn module"
+assert ref_render_utils.accumulate_along_rays is NC.accumulate_along_rays and ref_loss.accumulate_along_rays is NC.accumulate_along_rays
+from emernerf_amd.trainer import AABB, PROP_KW, model_config
+
+def describe(sd):
+    return [[k, list(v.shape), str(v.dtype), hashlib.sha256(v.detach().cpu().contiguous().numpy().tobytes()).hexdigest()]
+            for k, v in sd.items()]
+
+rec = {"models": {}, "props": []}
+for kind in ("static", "dynamic", "flow", "feature"):
+    torch.manual_seed(0)
+    ref = ref_build(model_config(kind, num_cams=3 if kind == "feature" else 1), verbose=False)
+    enc = ref.xyz_encoder.tcnn_encoding
+    assert type(enc) is amd_tcnn.Encoding and enc.params.numel() == enc.desc.n_entries * enc.desc.n_features
+    rec["models"][kind] = describe(ref.state_dict())
+for kw in PROP_KW:
+    torch.manual_seed(1)
+    rec["props"].append(describe(ref_density(aabb=AABB, unbounded=True, **kw).state_dict()))
+est = RefEstimator(None, None)
+assert isinstance(est, NC.AbstractEstimator) and est.device.type == "cpu"
+fn = get_proposal_requires_grad_fn()
+rec["proposal_schedule"] = {"steps": [0, 3000, 7], "requires_grad": [bool(fn(s)) for s in range(0, 3000, 7)]}
+print("SWAPS_RECORD " + json.dumps(rec))
+'''
+
+
+def run_import_swaps_case() -> dict:
+    import json
+    import subprocess
+    from emernerf_amd import _build
+    from oracle.ref_shims import REFERENCE_ROOT
+    _build.build()   # tcnn_modules.Encoding builds its grid descriptor in the library
+    r = subprocess.run([sys.executable, "-c", IMPORT_SWAPS_SCRIPT % {"root": ROOT, "ref": REFERENCE_ROOT}], capture_output=True,
+                       text=True, timeout=600, cwd=REFERENCE_ROOT, env={**os.environ, "PYTHONDONTWRITEBYTECODE": "1"})
+    line = [l for l in r.stdout.splitlines() if l.startswith("SWAPS_RECORD ")]
+    assert r.returncode == 0 and len(line) == 1, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
+    return json.loads(line[0][len("SWAPS_RECORD "):])
+
+
 RENDER_PIXELS_CASES = {
     "render_pixels_static": dict(kind="static", seed=800),
     "render_pixels_flow": dict(kind="flow", seed=900),
@@ -562,6 +639,13 @@ def main():
         path = os.path.join(HERE, "lidar_source.npz")
         np.savez_compressed(path, **out)
         print(f"lidar_source: {len(out)} arrays, {os.path.getsize(path) / 1e3:.0f} kB")
+    if not only or "import_swaps" in only:
+        import json
+        rec = run_import_swaps_case()
+        path = os.path.join(HERE, "import_swaps.json")
+        with open(path, "w") as f:   # one tensor per line
+            f.write(json.dumps(rec).replace("], [", "],\n[") + "\n")
+        print(f"import_swaps: {sum(len(v) for v in rec['models'].values())} model tensors, {os.path.getsize(path) / 1e3:.0f} kB")
     for name, kw in {**CASES, **TINTERP_CASES, **SHIPPED_CASES}.items():
         if only and name not in only:
             continue

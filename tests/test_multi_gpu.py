@@ -258,7 +258,7 @@ def test_bench_runs_with_two_ranks(hip_lib, tmp_path):
     env = dict(os.environ, EMER_BENCH_SHARE_GPU="1", EMER_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--init-steps", "7", "--rays", "1024", "--samples", "32"]
+           "--init-steps", "7", "--rays", "1024", "--samples", "32", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 D=/tmp/pc_${KIND}_${RAYS}; rm -rf $D
 STEPS=12
-timeout 400 rocprofv3 --kernel-trace --stats -d $D -o p --output-format csv -- python $R/bench.py --kind $KIND --rays $RAYS --eager --no-cpu-baseline \
+timeout 400 rocprofv3 --kernel-trace --stats -d $D -o p --output-format csv -- python $R/bench.py --full --kind $KIND --rays $RAYS --eager --no-cpu-baseline \
   --no-extras --no-second-state --no-secondary --no-fp16-state --steps $STEPS --warmup 2 --init-steps 14 > $OUT/${KIND}${RAYS}_bench_under_rocprof.log 2>&1
 cp $(find $D -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_${KIND}${RAYS}_kernel_stats.csv 2>/dev/null
 python - $D > $OUT/${TAG}_${KIND}${RAYS}_step_sequence.txt <<'P'

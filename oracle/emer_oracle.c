@@ -20,6 +20,7 @@
  * which spells every multiply/add explicitly (no FMA contraction).
  */
 #include <math.h>
+#include <omp.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -200,6 +201,147 @@ void orc_hashgrid_bwd_input(const orc_grid *g, const float *x, const float *para
             }
         }
         for (uint32_t d = 0; d < D; ++d) dx[n * D + d] = gx[d];
+    }
+}
+
+/* ---- value + error bound entry points (tests only) ---------------------------
+ * The same three grid operations as above, accumulated in double, each with the sum of the ABSOLUTE values of its terms: a
+ * kernel that forms the terms in fp32 and sums them in some order is then held per entry to |got - ref| <= c 2^-24 abs_sum,
+ * with c derived from its accumulation structure (tests/_bounds.py).  Weights are built in double from the fp32 fractions
+ * w = pos - floor(pos) (exact), which both sides share. */
+static inline void orc_cell(const orc_grid *g, uint32_t l, const float *xn, uint32_t *gi, double *w) {
+    for (uint32_t d = 0; d < g->n_dims; ++d) {
+        const float pos = fmaf(g->scale[l], xn[d], 0.5f);
+        const float fl = floorf(pos);
+        gi[d] = (uint32_t)(int32_t)fl;
+        w[d] = (double)(pos - fl);
+    }
+}
+
+/* Table gradient: grad (double), abs_sum = sum |wt go| and hits = (sample, corner) terms per entry (zero weights and zero
+ * dOut rows included).  Parallel within each level: small levels split the samples over the threads, each accumulating in a
+ * copy of its own (reduced afterwards); large levels split the ENTRIES, every thread walks all samples and adds the corners it
+ * owns (no atomics, no contention when many samples share a cell). */
+#define ORC_PRIVATE_MAX (1u << 16)  /* entries of a level up to which every thread keeps its own accumulators */
+static inline void orc_bwd_terms(const orc_grid *g, uint32_t l, const float *xn, const float *go, double *pg, double *pa,
+                                 uint32_t *ph, uint32_t lo, uint32_t hi) {
+    const uint32_t D = g->n_dims, F = g->n_features;
+    uint32_t gi[4]; double w[4];
+    orc_cell(g, l, xn, gi, w);
+    for (uint32_t m = 0; m < (1u << D); ++m) {
+        double wt = 1.0; uint32_t c[4];
+        for (uint32_t d = 0; d < D; ++d) {
+            if (m & (1u << d)) { wt *= w[d]; c[d] = gi[d] + 1u; }
+            else { wt *= 1.0 - w[d]; c[d] = gi[d]; }
+        }
+        const uint32_t idx = orc_grid_index(g, l, c);
+        if (idx < lo || idx >= hi) continue;
+        for (uint32_t f = 0; f < F; ++f) {
+            const double t = wt * (double)go[f];
+            pg[(size_t)idx * F + f] += t;
+            pa[(size_t)idx * F + f] += fabs(t);
+        }
+        ++ph[idx];
+    }
+}
+void orc_hashgrid_bwd_params_bound(const orc_grid *g, const float *x, const float *dout, double *grad, double *abs_sum,
+                                   uint32_t *hits, int64_t N) {
+    const uint32_t D = g->n_dims, L = g->n_levels, F = g->n_features;
+    memset(grad, 0, sizeof(double) * (size_t)g->n_entries * F);
+    memset(abs_sum, 0, sizeof(double) * (size_t)g->n_entries * F);
+    memset(hits, 0, sizeof(uint32_t) * (size_t)g->n_entries);
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t size = g->size[l];
+        double *lg = grad + (size_t)g->offset[l] * F, *la = abs_sum + (size_t)g->offset[l] * F;
+        uint32_t *lh = hits + g->offset[l];
+        if (size <= ORC_PRIVATE_MAX) {
+#pragma omp parallel
+            {
+                double *pg = (double *)calloc((size_t)size * F, sizeof(double));
+                double *pa = (double *)calloc((size_t)size * F, sizeof(double));
+                uint32_t *ph = (uint32_t *)calloc(size, sizeof(uint32_t));
+#pragma omp for schedule(static)
+                for (int64_t n = 0; n < N; ++n)
+                    orc_bwd_terms(g, l, x + n * D, dout + n * (int64_t)(L * F) + l * F, pg, pa, ph, 0u, size);
+#pragma omp critical
+                {
+                    for (size_t i = 0; i < (size_t)size * F; ++i) { lg[i] += pg[i]; la[i] += pa[i]; }
+                    for (uint32_t i = 0; i < size; ++i) lh[i] += ph[i];
+                }
+                free(pg); free(pa); free(ph);
+            }
+        } else {
+#pragma omp parallel
+            {
+                const int nt = omp_get_num_threads(), t = omp_get_thread_num();
+                const uint32_t lo = (uint32_t)((uint64_t)size * t / nt), hi = (uint32_t)((uint64_t)size * (t + 1) / nt);
+                for (int64_t n = 0; n < N; ++n)
+                    orc_bwd_terms(g, l, x + n * D, dout + n * (int64_t)(L * F) + l * F, lg, la, lh, lo, hi);
+            }
+        }
+    }
+}
+
+/* Input gradient in double, and per (row, dim) bound = sum over levels, corner pairs and features of
+ * |scale prod w| |go| (|e1| + |e0|): |e1| + |e0| rather than |e1 - e0|, so the bound holds whether a kernel forms the
+ * difference of the two corners first or sums the two halves of the Jacobian separately. */
+void orc_hashgrid_bwd_input_bound(const orc_grid *g, const float *x, const float *params, const float *dout, double *dx,
+                                  double *bound, int64_t N) {
+    const uint32_t D = g->n_dims, L = g->n_levels, F = g->n_features;
+#pragma omp parallel for schedule(static)
+    for (int64_t n = 0; n < N; ++n) {
+        double gx[4] = {0, 0, 0, 0}, bx[4] = {0, 0, 0, 0};
+        for (uint32_t l = 0; l < L; ++l) {
+            uint32_t gi[4]; double w[4];
+            orc_cell(g, l, x + n * D, gi, w);
+            const float *go = dout + n * (int64_t)(L * F) + l * F;
+            for (uint32_t gd = 0; gd < D; ++gd) {
+                for (uint32_t m = 0; m < (1u << (D - 1)); ++m) {
+                    double wt = (double)g->scale[l]; uint32_t c[4]; uint32_t bit = 0;
+                    for (uint32_t d = 0; d < D; ++d) {
+                        if (d == gd) { c[d] = gi[d]; continue; }
+                        if (m & (1u << bit)) { wt *= w[d]; c[d] = gi[d] + 1u; }
+                        else { wt *= 1.0 - w[d]; c[d] = gi[d]; }
+                        ++bit;
+                    }
+                    const float *e0 = params + ((size_t)g->offset[l] + orc_grid_index(g, l, c)) * F;
+                    c[gd] = gi[gd] + 1u;
+                    const float *e1 = params + ((size_t)g->offset[l] + orc_grid_index(g, l, c)) * F;
+                    for (uint32_t f = 0; f < F; ++f) {
+                        const double a = wt * (double)go[f];
+                        gx[gd] += a * ((double)e1[f] - (double)e0[f]);
+                        bx[gd] += fabs(a) * (fabs((double)e1[f]) + fabs((double)e0[f]));
+                    }
+                }
+            }
+        }
+        for (uint32_t d = 0; d < D; ++d) { dx[n * D + d] = gx[d]; bound[n * D + d] = bx[d]; }
+    }
+}
+
+/* Encoding in double, and sum |w v| per output element. */
+void orc_hashgrid_fwd_bound(const orc_grid *g, const float *x, const float *params, double *out, double *abs_out, int64_t N) {
+    const uint32_t D = g->n_dims, L = g->n_levels, F = g->n_features;
+#pragma omp parallel for schedule(static)
+    for (int64_t n = 0; n < N; ++n) {
+        for (uint32_t l = 0; l < L; ++l) {
+            uint32_t gi[4]; double w[4];
+            orc_cell(g, l, x + n * D, gi, w);
+            double acc[8] = {0}, ab[8] = {0};
+            for (uint32_t m = 0; m < (1u << D); ++m) {
+                double wt = 1.0; uint32_t c[4];
+                for (uint32_t d = 0; d < D; ++d) {
+                    if (m & (1u << d)) { wt *= w[d]; c[d] = gi[d] + 1u; }
+                    else { wt *= 1.0 - w[d]; c[d] = gi[d]; }
+                }
+                const float *e = params + ((size_t)g->offset[l] + orc_grid_index(g, l, c)) * F;
+                for (uint32_t f = 0; f < F; ++f) { acc[f] += wt * (double)e[f]; ab[f] += fabs(wt * (double)e[f]); }
+            }
+            for (uint32_t f = 0; f < F; ++f) {
+                out[n * (int64_t)(L * F) + l * F + f] = acc[f];
+                abs_out[n * (int64_t)(L * F) + l * F + f] = ab[f];
+            }
+        }
     }
 }
 

@@ -204,4 +204,8 @@ def cotrain(kind: str, device, K: int, rays: int, samples: int, prop_samples=(64
     res["n_sign_flipped"] = sum(v["n_sign_flipped"] for v in stats.values())
     res["n_table_entries"] = sum(v["numel"] for k, v in stats.items() if k.endswith("tcnn_encoding.params"))
     res["param_max_abs_diff"] = max(v["max_abs_diff"] for v in stats.values())
+    # every hash-table entry, the flipped ones included; and the sum of the K steps' learning rates (each side's Adam moves an
+    # entry by at most lr_k |m_hat / sqrt(v_hat)| per step: tests/test_train_parity_gpu.py bounds the difference with it)
+    res["table_max_abs_diff"] = max(v["max_abs_diff"] for k, v in stats.items() if k.endswith("tcnn_encoding.params"))
+    res["lr_sum"] = sum(tr.lr * lr_factor(k, num_iters) for k in range(K))
     return res

@@ -9,12 +9,17 @@ proposal-resampled ("training") sample positions, and one full optimizer step's 
 oracle/ref_path.py parameter by parameter.
 
 Tolerances (same as the small tests): grid forward 2e-6 abs; grid gradients 2e-5 x max; step gradients 2e-3 x max.
+On top of those, every grid output, table-gradient entry and input gradient is held to its own error bound
+|got - ref| <= c 2^-24 abs_sum against the double-precision oracle (tests/_bounds.py derives c per kernel path), and the
+owner-computes backward also runs on sample layouts built to reach its internal paths (layout_inputs).
 """
 import ctypes
 
 import numpy as np
 import pytest
 import torch
+
+from tests._bounds import assert_bound, c_forward, c_input_grad, c_sliced
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +32,7 @@ GRIDS = {
     "dynamic_xyzt": (4, 10, 32, 8192, 18, 4),      # default_config.yaml:70-77
     "flow_xyzt": (4, 10, 16, 4096, 18, 4),         # radiance_field.py:916-923 (has a DENSE level 0; the dynamic grid has none)
     "prop1": (3, 8, 16, 2048, 20, 1),              # default_config.yaml:51-58 (second proposal net)
+    "cfg0_static": (3, 4, 16, 2048, 19, 2),        # BASELINE configs[0]: 4 levels < 8 XCDs; level 1 (res 81, 81^3 > 2^19) barely hashed
 }
 
 _CACHE = {}
@@ -110,9 +116,15 @@ def test_hashgrid_metric_shape(hip_lib, oracle, name, dist):
     got_fwd = lm.detach().permute(1, 0, 2).reshape(N_METRIC, L * F).cpu().numpy()
     ref_fwd = oracle.hashgrid_fwd(meta, x, p)
     np.testing.assert_allclose(got_fwd, ref_fwd, rtol=0, atol=2e-6)
-    del got_fwd, ref_fwd
-    ref_dp = oracle.hashgrid_bwd_params(meta, x, dout)
+    del ref_fwd
+    ref64, fabs_ = oracle.hashgrid_fwd_bound(meta, x, p)
+    assert_bound(got_fwd, ref64, fabs_, c_forward(D), f"metric fwd {name}/{dist}", meta=meta, kind="fwd")
+    del got_fwd, ref64, fabs_
+    g64, gabs, hits = oracle.hashgrid_bwd_params_bound(meta, x, dout)
+    ref_dp = g64.astype(np.float32)   # (the double sum rounded once: what oracle.hashgrid_bwd_params returns, from exact terms)
     got_dp = pd.grad.cpu().numpy()
+    assert_bound(got_dp, g64, gabs, c_sliced(meta, desc, hits), f"metric bwd {name}/{dist}", meta=meta, hits=hits)
+    del g64, gabs
     scale = np.abs(ref_dp).max()
     err = np.abs(got_dp - ref_dp)
     assert err.max() <= 2e-5 * scale, f"{name}/{dist}: grid gradient max err {err.max():.3e} vs scale {scale:.3e} at {err.argmax()}"
@@ -125,6 +137,8 @@ def test_hashgrid_metric_shape(hip_lib, oracle, name, dist):
         ref_dx = oracle.hashgrid_bwd_input(meta, x, p, dout)
         sx = np.abs(ref_dx).max()
         np.testing.assert_allclose(xd.grad.cpu().numpy(), ref_dx, rtol=0, atol=2e-5 * sx)
+        dx64, bx = oracle.hashgrid_bwd_input_bound(meta, x, p, dout)
+        assert_bound(xd.grad.cpu().numpy(), dx64, bx, c_input_grad(D, L, F), f"metric dx {name}/{dist}", meta=meta, kind="dx")
 
 
 def test_hashgrid_sliced_is_run_to_run_stable(hip_lib, oracle):
@@ -213,6 +227,124 @@ def test_hashgrid_sliced_add_accumulates(hip_lib, oracle, name):
     torch.cuda.synchronize()
     want = a.double() + b.double()
     assert float((both.double() - want).abs().max()) <= 2e-6 * float(want.abs().max())
+    # the sum against the oracle: abs_sums and hits of the two evaluations add; the write-out of sliced_add rounds once more
+    ga, aa, ha = oracle.hashgrid_bwd_params_bound(meta, x1.cpu(), d1.permute(1, 0, 2).reshape(N1, -1).cpu())
+    gb, ab, hb = oracle.hashgrid_bwd_params_bound(meta, x2.cpu(), d2.permute(1, 0, 2).reshape(N2, -1).cpu())
+    hits = ha + hb
+    assert_bound(both.cpu().numpy(), ga + gb, aa + ab, c_sliced(meta, desc, hits, accumulate=True), f"sliced_add {name}", meta=meta, hits=hits)
+
+
+# ---------------------------------------------------------------------------- sample layouts that target the backward's paths
+LAYOUTS = ("point", "point_sparse", "shuffled", "cell_sorted", "lattice", "box", "ragged", "dead_rays")
+_POINT = (0.4123, 0.5871, 0.3319, 0.7019)
+
+
+def layout_inputs(layout: str, meta, n: int, seed: int):
+    """(x [n, D], dout [n, L*F]) of a sample layout (tests/test_kernels_gpu.py uses it at small n):
+    point         every sample at one interior position: runs far longer than a wave, ~n hits on 2^D entries per level;
+    point_sparse  the same with 1 in 64 samples elsewhere;
+    shuffled      the training batch in a random permutation: no runs, the second-pair queue busy;
+    cell_sorted   the training batch sorted by its cell on the finest level: the longest runs;
+    lattice       dyadic coordinates i / 2^k (k = 1..8) including exact 0, 1/2 and 1: corner weights exactly 0 or 1 on the levels
+                  whose scale makes scale x + 1/2 an integer (every odd integer scale at x = 1/2: level 0 of every grid);
+    box           a cube of side 4 / (finest resolution): a few coarse cells, many distinct fine ones;
+    ragged        the training batch cut to n (the metric test asks for 2^20 + 37: rows past 2^20 drawn uniformly);
+    dead_rays     the training batch with dOut exactly zero on whole 128-sample rays and on isolated samples."""
+    D, L, F = meta.n_dims, meta.n_levels, meta.n_features
+    g = torch.Generator().manual_seed(seed)
+
+    def training(k):
+        xs = _positions("training", D, 0)
+        if k <= xs.shape[0]:
+            return xs[:k].clone()
+        return torch.cat([xs, torch.rand(k - xs.shape[0], D, generator=g)])
+    if layout in ("point", "point_sparse"):
+        x = torch.tensor(_POINT[:D]).repeat(n, 1)
+        if layout == "point_sparse":
+            x[::64] = torch.rand(x[::64].shape, generator=g)
+    elif layout == "shuffled":
+        x = training(n)[torch.randperm(n, generator=g)]
+    elif layout == "cell_sorted":
+        x = training(n)
+        fine = (x.double() * float(meta.scale[-1]) + 0.5).float().floor().to(torch.int64).numpy()
+        x = x[torch.from_numpy(np.lexsort(tuple(fine[:, d] for d in range(D))))]
+    elif layout == "lattice":
+        k = torch.randint(1, 9, (n, D), generator=g)
+        i = (torch.rand(n, D, generator=g) * (2.0 ** k + 1)).floor()
+        x = (i / 2.0 ** k).float()
+        x[:3] = torch.tensor([0.0, 0.5, 1.0])[:, None]
+    elif layout == "box":
+        x = 0.37 + torch.rand(n, D, generator=g) * (4.0 / float(meta.res[-1]))
+    else:  # ragged, dead_rays
+        x = training(n)
+    dout = torch.randn(n, L * F, generator=g)
+    if layout == "dead_rays":
+        dead = (torch.arange(n) // 128) % 3 == 1
+        dead |= torch.rand(n, generator=g) < 0.02
+        dout[dead] = 0.0
+    return x.contiguous(), dout
+
+
+def sliced_layout_check(oracle, meta, desc, name: str, layout: str, x, dout, route: str = "one"):
+    """Forward (emitting the slice bitmaps) + owner-computes backward of one layout, against the per-entry bound of
+    tests/_bounds.py.  route: "one" (emer_hashgrid_bwd_params_sliced), "split" (the level ranges [k, L) then [0, k),
+    k = L // 2), "add" (the first half of the samples with sliced, the second added by sliced_add)."""
+    from emernerf_amd import _lib, ops
+    D, L, F = meta.n_dims, meta.n_levels, meta.n_features
+    n = x.shape[0]
+    dev = _dev()
+    p = (torch.rand(meta.n_params, generator=torch.Generator().manual_seed(3)) - 0.5).to(dev)
+    grad = torch.full((meta.n_params,), float("nan"), device=dev)   # every entry must be written
+    st = ops._stream(p)
+
+    def launch(xs, ds, fn, *extra):
+        k = xs.shape[0]
+        xd = xs.to(dev)
+        _, mk = ops.hashgrid_fwd_raw(desc, xd, p, level_major=True, want_masks=True)
+        dlm = ds.view(k, L, F).permute(1, 0, 2).contiguous().to(dev)
+        _lib.call(fn, ctypes.byref(desc), ops._ptr(xd), ops._ptr(dlm), F, k * F, ops._ptr(mk), ops._ptr(grad), k, *extra, st)
+        torch.cuda.synchronize()
+    if route == "one":
+        launch(x, dout, "emer_hashgrid_bwd_params_sliced")
+    elif route == "split":
+        launch(x, dout, "emer_hashgrid_bwd_params_sliced_levels", L // 2, L)
+        launch(x, dout, "emer_hashgrid_bwd_params_sliced_levels", 0, L // 2)
+    else:
+        h = n // 2
+        launch(x[:h].contiguous(), dout[:h].contiguous(), "emer_hashgrid_bwd_params_sliced")
+        launch(x[h:].contiguous(), dout[h:].contiguous(), "emer_hashgrid_bwd_params_sliced_add")
+    g64, gabs, hits = oracle.hashgrid_bwd_params_bound(meta, x, dout)
+    if route == "add":
+        # the write-out of sliced_add rounds once more; c of the sum uses the hits of both launches (= all of them)
+        c = c_sliced(meta, desc, hits, accumulate=True)
+    else:
+        c = c_sliced(meta, desc, hits)
+    return assert_bound(grad.cpu().numpy(), g64, gabs, c, f"layout {layout} {name} N={n} {route}", meta=meta, hits=hits)
+
+
+# grid x layout at the metric size: every layout on two or three grids, every grid under several layouts (the full 6 x 8
+# matrix runs at small N in tests/test_kernels_gpu.py); point on every grid (runs longer than a wave, one item doing all)
+METRIC_LAYOUTS = [("point", g) for g in GRIDS] + [
+    ("point_sparse", "cfg2_static"), ("point_sparse", "dynamic_xyzt"),
+    ("shuffled", "cfg2_static"), ("shuffled", "flow_xyzt"),
+    ("cell_sorted", "cfg0_static"), ("cell_sorted", "default_static"),
+    ("lattice", "cfg2_static"), ("lattice", "dynamic_xyzt"),
+    ("box", "prop1"), ("box", "cfg0_static"),
+    ("ragged", "cfg2_static"), ("ragged", "flow_xyzt"), ("ragged", "cfg0_static"),
+    ("dead_rays", "default_static"), ("dead_rays", "dynamic_xyzt"),
+]
+
+
+@pytest.mark.parametrize("layout,name", METRIC_LAYOUTS)
+def test_hashgrid_sliced_layouts_metric(hip_lib, oracle, layout, name):
+    """The owner-computes backward at N = 2^20 (ragged: 2^20 + 37) on sample layouts that drive its internal paths (see
+    layout_inputs), every table entry within c 2^-24 abs_sum of the double-precision oracle (c derived in tests/_bounds.py)."""
+    from emernerf_amd import ops
+    meta, desc = _mk(oracle, name)
+    assert ops.sliced_supported(desc)
+    n = N_METRIC + 37 if layout == "ragged" else N_METRIC
+    x, dout = layout_inputs(layout, meta, n, seed=41)
+    sliced_layout_check(oracle, meta, desc, name, layout, x, dout)
 
 
 # ------------------------------------------------------------------------------------------ fused heads

@@ -1,10 +1,13 @@
 """Kernel-level parity: every C-ABI entry point vs the CPU oracle on seeded inputs (MI355X only).
 
 Tolerances: sampler offsets bit-exact; everything else fp32 with the tolerance written at the check.
+Grid kernels in fp32 are also held per entry to c 2^-24 abs_sum of the double-precision oracle (tests/_bounds.py).
 """
 import numpy as np
 import pytest
 import torch
+
+from tests._bounds import assert_bound, c_atomic, c_forward, c_input_grad, c_sliced
 
 pytestmark = pytest.mark.gpu
 
@@ -15,6 +18,7 @@ GRIDS = {
     "dynamic_xyzt": (4, 10, 32, 8192, 18, 4),      # default_config.yaml:70-77
     "flow_xyzt": (4, 10, 16, 4096, 18, 4),         # radiance_field.py:916-923
     "prop0": (3, 8, 16, 512, 20, 1),               # default_config.yaml:51-58
+    "cfg0_static": (3, 4, 16, 2048, 19, 2),        # BASELINE configs[0]: fewer levels than XCDs; level 1 (res 81) barely hashed
     "tiny_f8": (3, 4, 4, 64, 10, 8),
     "tiny_2d": (2, 5, 8, 256, 12, 2),
 }
@@ -71,6 +75,9 @@ def test_hashgrid_fwd(hip_lib, oracle, name, n):
     # same fmaf cell + same corner order => only the FMA contraction of acc += w*v may differ
     np.testing.assert_allclose(rm.cpu().numpy(), ref, rtol=0, atol=2e-6)
     np.testing.assert_allclose(lm_as_rows, ref, rtol=0, atol=2e-6)
+    ref64, fabs_ = oracle.hashgrid_fwd_bound(meta, x, p)
+    assert_bound(rm.cpu().numpy(), ref64, fabs_, c_forward(meta.n_dims), f"fwd {name} n={n} row-major", meta=meta, kind="fwd")
+    assert_bound(lm_as_rows, ref64, fabs_, c_forward(meta.n_dims), f"fwd {name} n={n} level-major", meta=meta, kind="fwd")
     tr = ops.layout_transpose(lm, L, n, F, to_row_major=True)
     assert torch.equal(tr, rm)
     back = ops.layout_transpose(tr, L, n, F, to_row_major=False)
@@ -108,6 +115,8 @@ def test_hashgrid_fwd_is_independent_of_the_launch_size(hip_lib, oracle, name, h
                       ops._ptr(masks), ops._ptr(g_big), n, ops._stream(xd))
         ref_g = oracle.hashgrid_bwd_params(meta, x, dout.permute(1, 0, 2).reshape(n, -1).cpu())
         np.testing.assert_allclose(g_big.cpu().numpy(), ref_g, rtol=0, atol=2e-5 * float(np.abs(ref_g).max()))
+        g64, gabs, hits = oracle.hashgrid_bwd_params_bound(meta, x, dout.permute(1, 0, 2).reshape(n, -1).cpu())
+        assert_bound(g_big.cpu().numpy(), g64, gabs, c_sliced(meta, desc, hits), f"sliced bwd {name} n={n}", meta=meta, hits=hits)
 
 
 @pytest.mark.parametrize("name", ["cfg2_static", "dynamic_xyzt", "prop0", "tiny_f8", "tiny_2d"])
@@ -143,6 +152,12 @@ def test_hashgrid_backward(hip_lib, oracle, name):
     np.testing.assert_allclose(pd.grad.cpu().numpy(), ref_dp, rtol=0, atol=2e-5 * scale)
     sx = np.abs(ref_dx).max()
     np.testing.assert_allclose(xd.grad.cpu().numpy(), ref_dx, rtol=0, atol=2e-5 * sx)
+    g64, gabs, hits = oracle.hashgrid_bwd_params_bound(meta, x, dout)
+    c = c_sliced(meta, desc, hits) if ops.sliced_supported(desc) else c_atomic(meta.n_dims, hits)
+    assert_bound(pd.grad.cpu().numpy(), g64, gabs, c, f"bwd params {name}", meta=meta, hits=hits)
+    dx64, bx = oracle.hashgrid_bwd_input_bound(meta, x, p, dout)
+    assert_bound(xd.grad.cpu().numpy(), dx64, bx, c_input_grad(meta.n_dims, meta.n_levels, meta.n_features), f"bwd input {name}",
+                 meta=meta, kind="dx")
 
 
 @pytest.mark.parametrize("name", list(GRIDS))
@@ -179,6 +194,28 @@ def test_hashgrid_input_gradient_from_stored_jacobians(hip_lib, oracle, monkeypa
     sx = np.abs(ref_dx).max()
     np.testing.assert_allclose(got[True][1].cpu().numpy(), ref_dx, rtol=0, atol=2e-5 * sx)
     np.testing.assert_allclose(got[True][1].cpu().numpy(), got[False][1].cpu().numpy(), rtol=0, atol=2e-6 * sx)
+    dx64, bx = oracle.hashgrid_bwd_input_bound(meta, x, p, dout)
+    dx64[:skip] = 0.0   # skipped rows: zero bound, so exactly zero
+    bx[:skip] = 0.0
+    for jac in (True, False):
+        assert_bound(got[jac][1].cpu().numpy(), dx64, bx, c_input_grad(meta.n_dims, L, F), f"input grad {name} skip={skip} jac={jac}",
+                     meta=meta, kind="dx")
+
+
+@pytest.mark.parametrize("name", ["cfg2_static", "default_static", "dynamic_xyzt", "flow_xyzt", "prop0", "cfg0_static"])
+@pytest.mark.parametrize("layout", ["point", "point_sparse", "shuffled", "cell_sorted", "lattice", "box", "ragged", "dead_rays"])
+def test_hashgrid_sliced_layouts_small(hip_lib, oracle, name, layout):
+    """The owner-computes backward on the sample layouts of tests/test_a_metric_shape_gpu.layout_inputs at 20 000 samples (ragged:
+    1, 63 and 65 samples -- a partial last bitmap word, trip and workgroup), every table entry within the per-entry bound of
+    tests/_bounds.py; three layouts also through the level-range split and through sliced + sliced_add."""
+    from tests.test_a_metric_shape_gpu import layout_inputs, sliced_layout_check
+    meta, desc = _mk(oracle, name)
+    for n in ((1, 63, 65) if layout == "ragged" else (20000,)):
+        x, dout = layout_inputs(layout, meta, n, seed=43 + n)
+        sliced_layout_check(oracle, meta, desc, name, layout, x, dout)
+        if layout in ("point_sparse", "cell_sorted", "dead_rays"):
+            sliced_layout_check(oracle, meta, desc, name, layout, x, dout, route="split")
+            sliced_layout_check(oracle, meta, desc, name, layout, x, dout, route="add")
 
 
 def test_hashgrid_fp16_grads(hip_lib, oracle):

@@ -221,3 +221,73 @@ def test_ref_path_reproduces_reference_goldens(oracle, case):
         if "grad/" + k in gold:
             np.testing.assert_allclose(ref.t["model/" + k].grad.numpy(), gold["grad/" + k], rtol=1e-4,
                                        atol=1e-6 * np.abs(gold["grad/" + k]).max(), err_msg=k)
+
+
+# ------------------------------------------------------------------- value + error-bound entry points (tests/_bounds.py)
+@pytest.mark.parametrize("args", [(3, 16, 16, 2048, 19, 2), (3, 4, 16, 2048, 19, 2), (4, 10, 32, 8192, 18, 4), (3, 8, 16, 512, 20, 1),
+                                  (2, 5, 8, 256, 12, 2), (3, 4, 4, 64, 10, 8)])
+def test_bound_oracles_match_fp64_restatement(oracle, args):
+    """hashgrid_{fwd,bwd_params,bwd_input}_bound accumulate in double: they agree with hashgrid_torch run in float64 (same fp32
+    cells and fractions) to 1e-12 relative; abs_sum >= |value| everywhere; every level's hits sum to N 2^D (the index wraps
+    modulo the level size, so no corner falls outside the table); the rounded values meet the fp32 oracle."""
+    m = oracle.grid_meta_from_encoder_args(*args)
+    D, L, F = m.n_dims, m.n_levels, m.n_features
+    g = torch.Generator().manual_seed(11)
+    N = 3000
+    x = torch.rand(N, D, generator=g)
+    x[0] = 0.0; x[1] = 1.0; x[2] = 1.0 - 2 ** -24
+    x[3, 0] = -0.37; x[4, 0] = 1.61                    # outside [0, 1]: the index wraps
+    x[5:69] = x[5]                                      # a run of 64 equal samples
+    x[70:80] = torch.tensor([0.5, 0.25, 0.75, 0.125][:D])   # dyadic: weights exactly 0 / 1 on some levels
+    p = torch.rand(m.n_params, generator=g) - 0.5
+    do = torch.randn(N, L * F, generator=g)
+    do[7] = 0.0
+    xd, pd = x.double().requires_grad_(True), p.double().requires_grad_(True)
+    out = oracle.hashgrid_torch(xd, pd, m)
+    out.backward(do.double())
+
+    def rel_close(a, want, what):
+        want = want.detach().numpy()
+        assert np.abs(a - want).max() <= 1e-12 * max(np.abs(want).max(), 1e-300), what
+
+    fwd, fabs_ = oracle.hashgrid_fwd_bound(m, x, p)
+    rel_close(fwd, out, "fwd")
+    assert (fabs_ >= np.abs(fwd)).all()
+    np.testing.assert_allclose(fwd, oracle.hashgrid_fwd(m, x, p), rtol=0, atol=5e-7)
+    grad, abs_sum, hits = oracle.hashgrid_bwd_params_bound(m, x, do)
+    rel_close(grad, pd.grad, "grad")
+    assert (abs_sum >= np.abs(grad)).all()
+    assert grad.dtype == abs_sum.dtype == np.float64 and hits.shape == (m.n_entries,)
+    # the fp32-term oracles are paths of their own: terms wt * go rounded 2D times + one final rounding + slack -> 2D + 2; the
+    # forward is the kernel's loop (tests/_bounds.py c_forward)
+    from tests._bounds import assert_bound, c_forward
+    assert_bound(oracle.hashgrid_bwd_params(m, x, do), grad, abs_sum, 2 * D + 2, "fp32-term oracle grad", meta=m, hits=hits)
+    assert_bound(oracle.hashgrid_fwd(m, x, p), fwd, fabs_, c_forward(D), "fp32 oracle fwd", meta=m, kind="fwd")
+    for l in range(L):
+        a, b = int(m.offset[l]), int(m.offset[l] + m.size[l])
+        assert int(hits[a:b].astype(np.int64).sum()) == N * (1 << D), f"level {l}"
+        # an entry no term reached has neither value nor bound
+        untouched = np.repeat(hits[a:b] == 0, F)
+        assert (grad[a * F:b * F][untouched] == 0).all() and (abs_sum[a * F:b * F][untouched] == 0).all()
+    dx, bx = oracle.hashgrid_bwd_input_bound(m, x, p, do)
+    rel_close(dx, xd.grad, "dx")
+    assert (bx >= np.abs(dx)).all()
+    assert (dx[7] == 0).all() and (bx[7] == 0).all(), "a zero dOut row has zero gradient and zero bound"
+
+
+def test_bound_oracle_hits_count_each_corner():
+    """One sample at a dyadic point of a single dense level: the 2^D corners are 2^D distinct entries with one hit each, the
+    zero-weight corners carry hits but no abs_sum; the private-accumulator and atomic paths (levels below / above 2^16
+    entries) count alike."""
+    from oracle import oracle as O
+    for T, base in ((10, 9), (19, 65)):   # (scale 8, res 9: 736 entries, per-thread copies; scale 64, res 65: 274 632, atomics)
+        m = O.grid_meta(3, 1, 1, T, base, 1.0)
+        assert not m.hashed[0]
+        s = float(m.scale[0])
+        x = torch.tensor([[1.5 / s, 3.25 / s, 1.0 / s]], dtype=torch.float32)   # pos = (2, 3.75, 1.5): w = (0, 0.75, 0.5), exact
+        grad, abs_sum, hits = O.hashgrid_bwd_params_bound(m, x, torch.ones(1, 1))
+        assert int(hits.sum()) == 8 and hits.max() == 1
+        touched = hits > 0
+        nz = abs_sum > 0
+        assert nz.sum() == 4 and (touched[nz]).all(), "w_x == 0 exactly: the four x + 1 corners get zero weight"
+        np.testing.assert_allclose(grad.sum(), 1.0, rtol=1e-15)

@@ -132,6 +132,9 @@ SIGNATURES = {
     "emer_sample_importance": [_P, c_int64, _P, c_uint64, c_int64, _P, _P, _P],
     "emer_buffer_to_pixels": [_P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, c_uint64, _P, _P, _P, _P],
     "emer_gen_rays": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "emer_gather_pixel_extras": [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P],
+    "emer_ssim": [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P],
+    "emer_sq_err_sums": [_P, _P, _P, c_int64, c_int32, _P, _P, _P],
     "emer_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_int32, _P],
 }
 
@@ -144,6 +147,8 @@ INT64_FUNCTIONS = {
     "emer_rgb_head_bwd_fused_workspace": [c_int64, c_int32],
     "emer_density_bwd_fused_workspace": [c_int32, c_int32, c_int64],
     "emer_importance_sample_points_capacity": [],
+    "emer_ssim_workspace": [c_int32, c_int32],
+    "emer_sq_err_sums_workspace": [c_int64, c_int32],
 }
 
 ALLOW_MISSING_SYMBOLS = False  # never set by the product path

@@ -197,6 +197,33 @@ __global__ __launch_bounds__(256) void buffer_to_pixels_kernel(const int64_t *__
     y[i] = yy; x[i] = xx;
 }
 
+// dynamic mask and DINO-feature gathers of get_train_rays / get_render_rays (pixel_source.py:439-468,704-708,786-811): one
+// work item per (ray, 16-byte chunk of its feature row) -- consecutive lanes copy consecutive chunks of a row; the item of
+// chunk 0 also gathers the mask.  Feature coordinates are torch's float32 product truncated toward zero:
+// (y * downscale[0]).long() with y an int64 tensor and downscale a Python float.
+__global__ __launch_bounds__(256) void pixel_extras_kernel(const int64_t *__restrict__ img_idx, const int64_t *__restrict__ y,
+                                                           const int64_t *__restrict__ x, int64_t n, int32_t H, int32_t W,
+                                                           const float *__restrict__ dynamic_masks, const float *__restrict__ features,
+                                                           int32_t Hf, int32_t Wf, int32_t E, float scale_y, float scale_x,
+                                                           int32_t chunks, float *__restrict__ out_masks, float *__restrict__ out_features) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * chunks) return;
+    const int64_t ray = i / chunks;
+    const int32_t k = (int32_t)(i - ray * chunks);
+    const int64_t img = img_idx[ray], yy = y[ray], xx = x[ray];
+    if (k == 0 && dynamic_masks) out_masks[ray] = dynamic_masks[(img * H + yy) * W + xx];
+    if (!features) return;
+    int64_t fy = (int64_t)((float)yy * scale_y), fx = (int64_t)((float)xx * scale_x);
+    fy = fy < 0 ? 0 : (fy > Hf - 1 ? Hf - 1 : fy);   // (in range for every pixel of the image; kept inside the map regardless)
+    fx = fx < 0 ? 0 : (fx > Wf - 1 ? Wf - 1 : fx);
+    const int64_t src = ((img * Hf + fy) * Wf + fx) * E;
+    if ((E & 3) == 0) {
+        reinterpret_cast<float4 *>(out_features + ray * E)[k] = reinterpret_cast<const float4 *>(features + src)[k];
+    } else {
+        for (int32_t e = k; e < E; e += chunks) out_features[ray * E + e] = features[src + e];
+    }
+}
+
 }  // namespace emer
 
 using namespace emer;
@@ -214,6 +241,23 @@ extern "C" int emer_gen_rays(const int64_t *img_idx, const int64_t *y, const int
                   origins, viewdirs, direction_norms, pixel_coords, pixels, sky, ray_timestamps, ray_cam_ids};
     hipLaunchKernelGGL(gen_rays_kernel, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), a);
     return check_launch("gen_rays");
+}
+
+extern "C" int emer_gather_pixel_extras(const int64_t *img_idx, const int64_t *y, const int64_t *x, int64_t n, int32_t height, int32_t width,
+                                        const float *dynamic_masks, const float *features, int32_t feat_height, int32_t feat_width,
+                                        int32_t feat_dim, float scale_y, float scale_x, float *out_masks, float *out_features,
+                                        void *stream) {
+    EMER_REQUIRE(n >= 0 && height >= 1 && width >= 1, "gather_pixel_extras: bad sizes");
+    EMER_REQUIRE(!features || (feat_height >= 1 && feat_width >= 1 && feat_dim >= 1), "gather_pixel_extras: bad feature-map sizes");
+    if (n == 0 || (!dynamic_masks && !features)) return EMER_OK;
+    EMER_REQUIRE(img_idx && y && x && (!dynamic_masks || out_masks) && (!features || out_features), "gather_pixel_extras: null pointer");
+    EMER_REQUIRE(!features || (feat_dim & 3) != 0 || ((((uintptr_t)features | (uintptr_t)out_features) & 15) == 0),
+                 "gather_pixel_extras: feature buffers must be 16-byte aligned");
+    // chunks per ray: 16-byte chunks of the feature row (scalar copies when feat_dim % 4 != 0, 64 lanes' worth at most)
+    const int32_t chunks = !features ? 1 : ((feat_dim & 3) == 0 ? feat_dim / 4 : (feat_dim < 64 ? feat_dim : 64));
+    hipLaunchKernelGGL(pixel_extras_kernel, dim3((uint32_t)ceil_div(n * chunks, 256)), dim3(256), 0, as_stream(stream), img_idx, y, x, n, height,
+                       width, dynamic_masks, features, feat_height, feat_width, feat_dim, scale_y, scale_x, chunks, out_masks, out_features);
+    return check_launch("gather_pixel_extras");
 }
 
 extern "C" int emer_sample_uniform(const uint64_t *seed_word, uint64_t salt, int64_t n, const int64_t *candidates, int32_t n_candidates,

@@ -1257,3 +1257,64 @@ def blend_accumulate(weights: Tensor, density: Tensor, static_density: Tensor, d
     """sum_s w (sigma_s / (sigma + 1e-6) rgb_s (1 - shadow) + sigma_d / (sigma + 1e-6) rgb_d) and sum_s w shadow^2."""
     _check_cuda(weights, density, static_density, dynamic_density, static_rgb, dynamic_rgb, shadow_ratio)
     return _BlendAccumulateFn.apply(weights, density, static_density, dynamic_density, static_rgb, dynamic_rgb, shadow_ratio)
+
+
+# ------------------------------------------------------------------------------------ evaluation metrics
+def _metric_out(out: Optional[Tensor], like: Tensor) -> Tensor:
+    if out is None:
+        return torch.empty(3, dtype=torch.float64, device=like.device)
+    if out.dtype != torch.float64 or out.numel() != 3 or not out.is_contiguous() or out.device != like.device:
+        raise _lib.EmerError("metric output slot: 3 contiguous float64 elements on the images' device")
+    return out
+
+
+def _row_mask(mask: Optional[Tensor], rows: int) -> Optional[Tensor]:
+    """Any-dtype mask with ``rows`` elements -> contiguous fp32 whose nonzero entries mark the masked rows."""
+    if mask is None:
+        return None
+    if mask.numel() != rows:
+        raise _lib.EmerError(f"mask has {mask.numel()} elements, expected {rows}")
+    m = mask.detach().reshape(rows)
+    return (m if m.dtype == torch.float32 else (m != 0).to(torch.float32)).contiguous()
+
+
+def ssim(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, out: Optional[Tensor] = None, full: bool = False):
+    """SSIM of two [H, W, C] (or [H, W]) fp32 images, exactly as skimage.metrics.structural_similarity(pred, gt,
+    data_range=1.0, channel_axis=-1) computes it (emer_ssim).  Writes the device scalars (ssim, masked_sum, masked_count)
+    into ``out`` (3 contiguous float64 elements, e.g. a row slice of a caller tensor; allocated when None) without a host
+    sync: masked_sum is the sum of the uncropped S map over the pixels x channels where ``mask`` ([H, W] or [H, W, 1], any
+    dtype) is nonzero and masked_count their number, so masked_sum / masked_count is
+    ``structural_similarity(..., full=True)[1][mask].mean()``.  Returns ``out``, or ``(out, S map [H, W, C])`` when ``full``.
+    H < 7 or W < 7 raises, as in scikit-image."""
+    _check_cuda(pred, gt, mask, out)
+    if pred.shape != gt.shape or pred.dim() not in (2, 3):
+        raise _lib.EmerError(f"ssim: need two [H, W, C] images of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    H, W = pred.shape[:2]
+    C = pred.shape[2] if pred.dim() == 3 else 1
+    x, y = _f32c(pred), _f32c(gt)
+    m = _row_mask(mask, H * W)
+    res = _metric_out(out, x)
+    smap = torch.empty_like(x) if full else None
+    with torch.cuda.device(x.device):
+        ws = torch.empty(max(int(_lib.load().emer_ssim_workspace(H, W)), 1), dtype=torch.float64, device=x.device)
+        _lib.call("emer_ssim", _ptr(x), _ptr(y), _ptr(m), H, W, C, _ptr(smap), _ptr(ws), _ptr(res), _stream(x))
+    return (res, smap) if full else res
+
+
+def sq_err_sums(pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """(sum of (pred - target)^2, the same over the rows whose ``mask`` entry is nonzero, the number of such rows) in float64
+    on the device (emer_sq_err_sums), for pred / target of shape [..., cols] fp32 and a mask with one entry per row (any
+    dtype).  Written into ``out`` (3 contiguous float64 elements; allocated when None) without a host sync: mse =
+    sum / (rows * cols), masked mse = masked_sum / (n_rows * cols)."""
+    _check_cuda(pred, target, mask, out)
+    if pred.shape != target.shape or pred.dim() < 1:
+        raise _lib.EmerError(f"sq_err_sums: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
+    cols = pred.shape[-1]
+    rows = pred.numel() // max(cols, 1)
+    p, t = _f32c(pred), _f32c(target)
+    m = _row_mask(mask, rows)
+    res = _metric_out(out, p)
+    with torch.cuda.device(p.device):
+        ws = torch.empty(max(int(_lib.load().emer_sq_err_sums_workspace(rows, cols)), 1), dtype=torch.float64, device=p.device)
+        _lib.call("emer_sq_err_sums", _ptr(p), _ptr(t), _ptr(m), rows, cols, _ptr(ws), _ptr(res), _stream(p))
+    return res

@@ -7,7 +7,8 @@ Loading images / poses from disk (the dataset classes proper) stays out of scope
 reference's loaders produce.
 
 Every per-batch operation is a HIP kernel (csrc/rays.hip): one launch for uniform pixels, a radix-select race for the
-error-buffer multinomial (no host round trip), one gather kernel for rays + colours + masks + timestamps.  Random numbers
+error-buffer multinomial (no host round trip), one gather kernel for rays + colours + masks + timestamps, and (when the
+source has them) one more for the dynamic masks and the DINO feature rows (``get_features``, :439-468).  Random numbers
 come from a counter-based generator keyed by a seed word in device memory (``self.seed_word``), advanced by one tiny
 device op per batch, so a captured hipGraph replays with fresh rays.
 """
@@ -49,12 +50,16 @@ def get_rays(x: Tensor, y: Tensor, c2w: Tensor, intrinsic: Tensor) -> Tuple[Tens
 
 class PixelSource:
     """images [n_imgs,H,W,3] fp32 in [0,1], cam_to_worlds [n_imgs,4,4], intrinsics [n_imgs,3,3] (all on the GPU);
-    optional sky_masks [n_imgs,H,W], normalized_timestamps [n_imgs], cam_ids [n_imgs]."""
+    optional sky_masks [n_imgs,H,W], normalized_timestamps [n_imgs], cam_ids [n_imgs]; keyword-only dynamic_masks
+    [n_imgs,H,W] (any dtype, stored as float like the reference's loader, :256-268) and features [n_imgs,Hf,Wf,E] (DINO
+    feature maps, stored fp32 on the device).  A feature row is looked up at ((y * Hf / H).long(), (x * Wf / W).long()) in
+    torch's float32 arithmetic (``featmap_downscale_factor``, :318-321)."""
 
     def __init__(self, images: Tensor, cam_to_worlds: Tensor, intrinsics: Tensor, sky_masks: Optional[Tensor] = None,
                  normalized_timestamps: Optional[Tensor] = None, cam_ids: Optional[Tensor] = None, buffer_ratio: float = 0.0,
-                 buffer_downscale: int = 4, seed: int = 0) -> None:
-        _check_cuda(images, cam_to_worlds, intrinsics, sky_masks, normalized_timestamps, cam_ids)
+                 buffer_downscale: int = 4, seed: int = 0, *, dynamic_masks: Optional[Tensor] = None,
+                 features: Optional[Tensor] = None) -> None:
+        _check_cuda(images, cam_to_worlds, intrinsics, sky_masks, normalized_timestamps, cam_ids, dynamic_masks, features)
         self.images = images.float().contiguous()
         self.num_imgs, self.HEIGHT, self.WIDTH = self.images.shape[:3]
         self.cam_to_worlds = cam_to_worlds.float().contiguous()
@@ -62,6 +67,15 @@ class PixelSource:
         self.sky_masks = None if sky_masks is None else sky_masks.float().contiguous()
         self.normalized_timestamps = None if normalized_timestamps is None else normalized_timestamps.float().contiguous()
         self.cam_ids = None if cam_ids is None else cam_ids.to(torch.int64).contiguous()
+        self.dynamic_masks = None if dynamic_masks is None else dynamic_masks.float().contiguous()
+        if self.dynamic_masks is not None and tuple(self.dynamic_masks.shape) != (self.num_imgs, self.HEIGHT, self.WIDTH):
+            raise ValueError(f"dynamic_masks: expected {(self.num_imgs, self.HEIGHT, self.WIDTH)}, got {tuple(self.dynamic_masks.shape)}")
+        self.features = None if features is None else features.float().contiguous()
+        self.featmap_downscale_factor = None
+        if self.features is not None:
+            if self.features.dim() != 4 or self.features.shape[0] != self.num_imgs:
+                raise ValueError(f"features: expected [{self.num_imgs}, Hf, Wf, E], got {tuple(self.features.shape)}")
+            self.featmap_downscale_factor = (self.features.shape[1] / self.HEIGHT, self.features.shape[2] / self.WIDTH)
         self.device = self.images.device
         self.buffer_ratio, self.buffer_downscale = float(buffer_ratio), int(buffer_downscale)
         self.pixel_error_maps: Optional[Tensor] = None
@@ -168,6 +182,22 @@ class PixelSource:
             out["cam_idx"] = cam
         if sky is not None:
             out["sky_masks"] = sky
+        if self.dynamic_masks is not None or self.features is not None:
+            dyn = torch.empty(n, device=dev) if self.dynamic_masks is not None else None
+            feat = None
+            Hf = Wf = E = 0
+            sy = sx = 0.0
+            if self.features is not None:
+                _, Hf, Wf, E = self.features.shape
+                sy, sx = self.featmap_downscale_factor
+                feat = torch.empty((n, E), device=dev)
+            with torch.cuda.device(dev):
+                _lib.call("emer_gather_pixel_extras", _ptr(img_idx), _ptr(y), _ptr(x), n, self.HEIGHT, self.WIDTH, _ptr(self.dynamic_masks),
+                          _ptr(self.features), Hf, Wf, E, sy, sx, _ptr(dyn), _ptr(feat), _stream(img_idx))
+            if dyn is not None:
+                out["dynamic_masks"] = dyn
+            if feat is not None:
+                out["features"] = feat
         return out
 
     def get_train_rays(self, num_rays: int, candidate_indices=None) -> Dict[str, Tensor]:
@@ -193,7 +223,7 @@ class PixelSource:
         y, x = self._all
         out = self._gather(torch.full((H * W,), int(img_idx), dtype=torch.int64, device=dev), y, x)
         out["direction_norm"] = out.pop("direction_norms")   # the reference's render dict spells this key in the singular (:836)
-        return {k: v.reshape(H, W, -1).squeeze(-1) if k in ("normed_timestamps", "img_idx", "cam_idx", "sky_masks") else v.reshape(H, W, -1)
+        return {k: v.reshape(H, W, -1).squeeze(-1) if k in ("normed_timestamps", "img_idx", "cam_idx", "sky_masks", "dynamic_masks") else v.reshape(H, W, -1)
                 for k, v in out.items()}
 
     def __len__(self) -> int:
@@ -205,9 +235,12 @@ class PixelSource:
     # -------------------------------------------------------------------------------------------- synthetic data
     @classmethod
     def synthetic(cls, device, num_imgs: int = 50, height: int = 160, width: int = 240, num_cams: int = 1, seed: int = 0,
-                  buffer_ratio: float = 0.0) -> "PixelSource":
+                  buffer_ratio: float = 0.0, dynamic_ratio: float = 0.0, feature_dim: int = 0,
+                  feature_hw: Optional[Tuple[int, int]] = None) -> "PixelSource":
         """A seeded stand-in for a driving log (no dataset on the box): a camera moving along +x through the scene box of
-        configs/default_config.yaml, random images, 15 % sky."""
+        configs/default_config.yaml, random images, 15 % sky.  ``dynamic_ratio`` > 0: random dynamic masks covering that
+        share of the pixels; ``feature_dim`` > 0: random [feature_hw] x feature_dim feature maps (default 1/8 of the image
+        size).  Both are drawn after everything else, so the data without them stays the same bit for bit."""
         g = torch.Generator().manual_seed(seed)
         n_t = num_imgs // num_cams
         c2w = torch.eye(4).repeat(num_imgs, 1, 1)
@@ -225,5 +258,10 @@ class PixelSource:
         sky = (torch.rand(num_imgs, height, width, generator=g) < 0.15).float()
         ts = (torch.arange(num_imgs) // num_cams).float() / max(n_t - 1, 1)
         cams = torch.arange(num_imgs) % num_cams
+        dyn = (torch.rand(num_imgs, height, width, generator=g) < dynamic_ratio).float().to(device) if dynamic_ratio > 0 else None
+        feats = None
+        if feature_dim > 0:
+            hf, wf = feature_hw if feature_hw is not None else (max(height // 8, 1), max(width // 8, 1))
+            feats = torch.rand(num_imgs, hf, wf, feature_dim, generator=g).to(device)
         return cls(images.to(device), c2w.to(device), K.to(device), sky.to(device), ts.to(device), cams.to(device),
-                   buffer_ratio=buffer_ratio, seed=seed)
+                   buffer_ratio=buffer_ratio, seed=seed, dynamic_masks=dyn, features=feats)

@@ -7,19 +7,21 @@ gt_rgbs, depths, opacities, static_* / dynamic_* decomposition, shadow_reduced_s
 
 What changed underneath: an image's rays come from ``PixelSource.get_render_rays`` (one gather kernel), all chunks of an
 image are rendered before any result leaves the GPU, an image's results leave it as ONE asynchronous transfer that overlaps
-the next image's rendering (the reference interleaves a blocking ``.cpu().numpy()`` per key with the rendering), and PSNR is
-computed on the device.  Out of scope here, as in SURVEY section 2: video encoding, SSIM (scikit-image), DINO-feature PCA colouring.
+the next image's rendering (the reference interleaves a blocking ``.cpu().numpy()`` per key with the rendering), and the
+metrics -- PSNR, SSIM (scikit-image's algorithm, csrc/metrics.hip), feature PSNR and their dynamic-mask variants -- are
+computed on the device and read back once after the loop.  Out of scope here: video encoding, DINO-feature PCA colouring.
 """
 from __future__ import annotations
 
 import logging
 import time
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from . import ops
 from .prop_net import PropNetEstimator
 from .radiance_field import DensityField, RadianceField
 from .render_utils import render_rays
@@ -86,7 +88,13 @@ def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimato
     results = render(dataset, render_func, model=model, compute_metrics=compute_metrics, vis_indices=vis_indices)
     if compute_metrics:
         n = len(dataset) if vis_indices is None else len(vis_indices)
-        logger.info(f"Eval over {n} images:\n\tPSNR: {results['psnr']:.4f}")
+        logger.info(f"Eval over {n} images:")
+        logger.info(f"\tPSNR: {results['psnr']:.4f}")
+        logger.info(f"\tSSIM: {results['ssim']:.4f}")
+        logger.info(f"\tFeature PSNR: {results['feat_psnr']:.4f}")
+        logger.info(f"\tMasked PSNR: {results['masked_psnr']:.4f}")
+        logger.info(f"\tMasked SSIM: {results['masked_ssim']:.4f}")
+        logger.info(f"\tMasked Feature PSNR: {results['masked_feat_psnr']:.4f}")
     return results
 
 
@@ -94,9 +102,14 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
            vis_indices: Optional[List[int]] = None) -> Dict[str, list]:
     """video_utils.py:109-468: the reference's result dictionary key for key -- the nine lists it always returns (possibly
     empty), the conditional ones (gt_rgbs, gt_sky_masks, shadow_*, forward_flows / backward_flows, median_depths), the
-    scalars (psnr; ssim and the feature / masked metrics are -1: SSIM and the DINO-feature PCA colouring are out of scope,
-    SURVEY section 2).  ``forward_flows`` / ``backward_flows`` hold the rendered flow (the reference stores its colour-wheel
-    visualisation).  Checked against a recording of the reference's own loop: tests/golden/render_pixels_*.npz."""
+    scalars psnr, ssim, feat_psnr, masked_psnr, masked_ssim, masked_feat_psnr under the reference's rules (:206-247,421-428):
+    ssim of every image with ground truth; masked_* only for images whose ``dynamic_masks`` has a nonzero entry; feat_psnr /
+    masked_feat_psnr only where the results carry ``dino_feat`` and the data ``features``; each the mean over the images that
+    contributed, -1 when none did, and all -1 when ``compute_metrics`` is False.  Per-image values stay in a device tensor
+    and are read back once, after the loop.  One deliberate deviation: an image smaller than 7 x 7 is left out of ssim /
+    masked_ssim (a warning is logged once), where scikit-image raises.  The DINO-feature PCA colouring lists are not
+    produced.  ``forward_flows`` / ``backward_flows`` hold the rendered flow (the reference stores its colour-wheel
+    visualisation).  Checked against recordings of the reference's own loop: tests/golden/render_pixels_*.npz."""
     always = ["rgbs", "static_rgbs", "dynamic_rgbs", "depths", "opacities", "static_depths", "static_opacities", "dynamic_depths",
               "dynamic_opacities"]
     out: Dict[str, list] = {v: [] for v in _COLLECT.values()}
@@ -106,9 +119,16 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
     pinned: Dict[int, Tensor] = {}
     n_rays, n_images, t0 = 0, 0, time.perf_counter()
     green = None
+    # per-image metrics on the device, one row per image: ssim (value, masked S sum, masked count) | colour squared-error sums
+    # (all, masked, masked rows) | feature squared-error sums (same); read back once after the loop
+    metrics: Optional[Tensor] = None
+    ssim_rows: List[int] = []
+    rgb_mask_rows: List[Tuple[int, int]] = []          # (row, colour channels)
+    feat_rows: List[Tuple[int, int, int]] = []         # (row, pixels, feature dim)
+    warned_small = False
     with torch.no_grad():
         indices = vis_indices if vis_indices is not None else range(len(dataset))
-        for i in indices:
+        for j, i in enumerate(indices):
             data = {k: (v.cuda(non_blocking=True) if isinstance(v, Tensor) and not v.is_cuda else v) for k, v in dataset[i].items()}
             res = render_func(data)
             n_rays += int(data["origins"].numel() // 3)
@@ -128,6 +148,25 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
                 keep["gt_sky_masks"] = data["sky_masks"]
             if compute_metrics and "pixels" in data:  # stays on the device until the loop is over (no sync per image)
                 psnrs.append(-10.0 * torch.log10(torch.nn.functional.mse_loss(res["rgb"], data["pixels"])))
+                if metrics is None:
+                    metrics = torch.zeros((len(indices), 9), dtype=torch.float64, device=res["rgb"].device)
+                mask = data.get("dynamic_masks")
+                H, W = res["rgb"].shape[:2]
+                if H >= 7 and W >= 7:
+                    ops.ssim(res["rgb"], data["pixels"], mask, out=metrics[j, 0:3])
+                    ssim_rows.append(j)
+                elif not warned_small:
+                    logger.warning(f"render: {H} x {W} images are smaller than the 7 x 7 SSIM window; ssim / masked_ssim leave them out")
+                    warned_small = True
+                if mask is not None:
+                    ops.sq_err_sums(res["rgb"], data["pixels"], mask, out=metrics[j, 3:6])
+                    rgb_mask_rows.append((j, res["rgb"].shape[-1]))
+            if compute_metrics and "dino_feat" in res and "features" in data:
+                if metrics is None:
+                    metrics = torch.zeros((len(indices), 9), dtype=torch.float64, device=res["dino_feat"].device)
+                E = res["dino_feat"].shape[-1]
+                ops.sq_err_sums(res["dino_feat"], data["features"], data.get("dynamic_masks"), out=metrics[j, 6:9])
+                feat_rows.append((j, res["dino_feat"].numel() // E, E))
             # ONE device->host transfer per image: every kept tensor packed into a flat buffer, copied asynchronously into
             # pinned memory and unpacked while the NEXT image renders (the reference interleaves a blocking .cpu().numpy() per
             # key with the rendering; on a slow host that halves the loop's throughput)
@@ -137,11 +176,43 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
                 _unpack(pending.pop(0), out)
         while pending:
             _unpack(pending.pop(0), out)
+        # the one read-back of every metric: the psnr mean (fp32, as before) and the per-image rows
+        host = None
+        if psnrs or metrics is not None:
+            parts = [torch.stack(psnrs).mean().double().reshape(1)] if psnrs else []
+            if metrics is not None:
+                parts.append(metrics.reshape(-1))
+            host = torch.cat(parts).cpu().numpy()
     torch.cuda.synchronize()
     out = {k: v for k, v in out.items() if len(v) > 0 or k in always}
     dt = time.perf_counter() - t0
     out["render_rays_per_s"] = n_rays / dt if dt > 0 else float("nan")
-    out["psnr"] = (float(torch.stack(psnrs).mean()) if psnrs else -1.0) if compute_metrics else -1
-    for k in ("ssim", "feat_psnr", "masked_psnr", "masked_ssim", "masked_feat_psnr"):
-        out[k] = -1
+    out["psnr"] = (float(host[0]) if psnrs else -1.0) if compute_metrics else -1
+    ssims, masked_ssims, masked_psnrs, feat_psnrs, masked_feat_psnrs = [], [], [], [], []
+    if metrics is not None:
+        m = host[len(host) - metrics.numel():].reshape(metrics.shape)
+        for j in ssim_rows:
+            ssims.append(float(m[j, 0]))
+            if m[j, 2] > 0:   # an image whose mask has a nonzero entry
+                masked_ssims.append(float(m[j, 1] / m[j, 2]))
+        for j, c in rgb_mask_rows:
+            if m[j, 5] > 0:
+                masked_psnrs.append(_psnr(m[j, 4], m[j, 5] * c))
+        for j, n, e in feat_rows:
+            feat_psnrs.append(_psnr(m[j, 6], n * e))
+            if m[j, 8] > 0:
+                masked_feat_psnrs.append(_psnr(m[j, 7], m[j, 8] * e))
+    for k, v in (("ssim", ssims), ("feat_psnr", feat_psnrs), ("masked_psnr", masked_psnrs), ("masked_ssim", masked_ssims),
+                 ("masked_feat_psnr", masked_feat_psnrs)):
+        out[k] = _non_zero_mean(v) if compute_metrics else -1
     return out
+
+
+def _non_zero_mean(x: List[float]) -> float:
+    """video_utils.py:45-47."""
+    return sum(x) / len(x) if len(x) > 0 else -1
+
+
+def _psnr(sq_sum: float, n: float) -> float:
+    """datasets/metrics.py:31-46 from a squared-error sum over n entries."""
+    return float(-10.0 * np.log10(sq_sum / n))

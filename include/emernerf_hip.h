@@ -737,6 +737,35 @@ int emer_gen_rays(const int64_t *img_idx, const int64_t *y, const int64_t *x, co
                   float *viewdirs, float *direction_norms, float *pixel_coords, float *pixels, float *sky,
                   float *ray_timestamps, int64_t *ray_cam_ids, void *stream);
 
+/* Dynamic-mask and feature gathers of get_train_rays / get_render_rays (pixel_source.py:439-468,704-708,786-811), one
+ * launch next to emer_gen_rays for the same (img, y, x): out_masks[i] = dynamic_masks[img,y,x] ([n_imgs,H,W] fp32) and
+ * out_features[i,:] = features[img, fy, fx, :] ([n_imgs,feat_height,feat_width,feat_dim] fp32) with
+ * fy = (int64)((float)y * scale_y), fx likewise (torch's float32 product, truncated).  Either tensor may be NULL (its output
+ * is then not written).  feat_dim % 4 == 0: 16-byte copies, both feature buffers 16-byte aligned.  No allocation, no sync. */
+int emer_gather_pixel_extras(const int64_t *img_idx, const int64_t *y, const int64_t *x, int64_t n, int32_t height,
+                             int32_t width, const float *dynamic_masks, const float *features, int32_t feat_height,
+                             int32_t feat_width, int32_t feat_dim, float scale_y, float scale_x, float *out_masks,
+                             float *out_features, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics (radiance_fields/video_utils.py:206-247), results left on the device.
+ * ---------------------------------------------------------------------------------------------- */
+/* SSIM of pred vs gt ([height,width,channels] fp32) exactly as skimage.metrics.structural_similarity(pred, gt,
+ * data_range=1.0, channel_axis=-1) computes it (7x7 uniform window, reflect borders, sample covariance, fp64 moments):
+ * out[0] = the SSIM (mean of the S map cropped by 3 pixels, over channels), out[1] = sum of the uncropped S over the
+ * pixels x channels where mask ([height,width] fp32, may be NULL) is nonzero, out[2] = their count (fp64).  ssim_map
+ * ([height,width,channels] fp32) may be NULL.  height, width >= 7 (EMER_E_INVALID otherwise).  Workspace:
+ * emer_ssim_workspace(height, width) doubles.  Two launches, fixed-order reduction: bitwise reproducible. */
+int64_t emer_ssim_workspace(int32_t height, int32_t width);
+int emer_ssim(const float *pred, const float *gt, const float *mask, int32_t height, int32_t width, int32_t channels,
+              float *ssim_map, double *workspace, double *out, void *stream);
+/* Squared-error sums of pred vs target ([rows,cols] fp32) in fp64: out[0] = sum over all entries, out[1] = sum over the
+ * rows whose row_mask ([rows] fp32, may be NULL) is nonzero, out[2] = the number of such rows.  Workspace:
+ * emer_sq_err_sums_workspace(rows, cols) doubles.  Two launches, fixed-order reduction: bitwise reproducible. */
+int64_t emer_sq_err_sums_workspace(int64_t rows, int32_t cols);
+int emer_sq_err_sums(const float *pred, const float *target, const float *row_mask, int64_t rows, int32_t cols,
+                     double *workspace, double *out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam as configured in builders.py:50-60,114-120: eps 1e-15,
  * betas (0.9, 0.99), weight_decay as L2) over one flat fp32 buffer; grad_scale multiplies the

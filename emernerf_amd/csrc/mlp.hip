@@ -6,8 +6,9 @@
 //
 // Precision: v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 -- f32 in, f32 accumulate, bit-identical
 // to a k-ordered fmaf chain (MI355X guide, "FP32-input MFMA"), so the heads keep the reference's
-// fp32 semantics (north-star tolerance 1e-4 on composited RGB/depth) while running on the matrix
-// pipe at the full fp32 rate and leaving the VALU free for bias/activation epilogues.
+// fp32 semantics while running on the matrix pipe at the full fp32 rate and leaving the VALU free
+// for bias/activation epilogues.  Tests: tests/test_head_exact_gpu.py (exact grid probes, the
+// trunc_exp clamp) and the per-entry bounds of tests/_bounds.py.
 //
 // Kernels
 //   linear_fwd  : Y = act(X W^T + b).  128-row workgroup tile, 4 waves x 32 rows; 64-wide (32x32x2)

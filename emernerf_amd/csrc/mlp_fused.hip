@@ -17,7 +17,8 @@
 // order <= 2^-16 -- w_l x_h, w_h x_l, w_m x_m, w_m x_h, w_h x_m, w_h x_h, smallest first -- on
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  bf16 x bf16 is exact in fp32; the dropped terms (w_m x_l, w_l x_m,
 // w_l x_l) are <= 2^-23 relative per product, i.e. the result differs from an fp32 FMA chain by fp32-roundoff-sized
-// errors (tests: same tolerances as the fp32 kernels of round 2, 1e-4 forward / 2e-4 gradients vs fp64).  Six K = 32
+// errors (tests: tests/test_head_exact_gpu.py holds grid inputs to the bitwise fp64 result, one probe per plane pair;
+// tests/test_head_bounds_cpu.py shows each dropped product or plane fails a probe).  Six K = 32
 // instructions of 16 cycles replace eight K = 4 instructions of 32 cycles: 0.375x the matrix time.  Non-finite inputs
 // give NaN (inf - inf in the split) where an fp32 product would give inf.
 //

@@ -17,6 +17,7 @@ owner-computes backward (hits * 2^-53 relative, below 2^-24 for fewer than 2^29 
 import ctypes
 
 import numpy as np
+import torch
 
 U = 2.0 ** -24
 
@@ -135,3 +136,124 @@ def assert_bound(got, ref, abs_sum, c, what: str, meta=None, kind: str = "params
     if report is not None:
         report[what] = worst
     return worst
+
+
+# ------------------------------------------------------------------------------------------------- MLP head kernels
+# The heads' GEMMs (csrc/mlp.hip, csrc/mlp_fused.hip) are held to the same form: a layer's own error is at most
+# c u abs_sum with abs_sum = sum_k |a| |b| + |bias|, and the error its inputs already carry is propagated to first order
+# through |W| (ReLU is 1-Lipschitz, sigmoid 1/4-Lipschitz, exp multiplies by its value).  ``head_*`` below do this
+# propagation in fp64 torch, next to the fp64 reference values, and ``assert_head_bound`` checks every entry; an entry whose
+# bound is 0 must come out exactly 0.
+#
+# Assumption: how one MFMA instruction rounds its internal sum on MI355X has not been measured, so every c below counts
+# one round-to-nearest rounding PER ADDITION (a sum of n terms in any order -- sequential, tree, across waves, partials,
+# atomics -- puts each term through at most n - 1 roundings).  A matrix instruction that truncated internally instead
+# would need about twice these c.  The count is loose: the bound does NOT catch a dropped partial product or an empty l
+# plane (tests/test_head_bounds_cpu.py prints how far inside it such mutants stay).  Only the exact probes of
+# tests/test_head_exact_gpu.py discriminate those; the bounds hold random inputs entry by entry, small entries included.
+
+C_EXP = 4.0   # expf (OCML, <= 1 ulp = 2 u relative) of an exactly formed x - 1: 4 u relative to the value
+C_SIG = 8.0   # 1 / (1 + expf(-x)): expf 2 u, the add and the division u each -> 4 u first order; slack x 2
+
+
+def c_head_bf16x3(k: int) -> float:
+    """A sum of k fp32 products (+ the bias) on the bf16 matrix pipe (tgemm, the neck / rgb / rmlp / density kernels, the
+    streamed and fused weight gradients): a product a b becomes six exact bf16 x bf16 partial products; the dropped
+    w_m x_l + w_l x_m + w_l x_l and the two operands' split remainders are <= 4 u |a| |b| together.  6 k partial products
+    + the bias are summed in fp32: 6 k roundings.  Slack 1  ->  6 k + 5.  It also bounds the fp32 paths (k + 2 below),
+    so the GPU tests use it wherever the path taken depends on the shape."""
+    return float(6 * k + 5)
+
+
+def c_head_fp32(k: int) -> float:
+    """fp32-input MFMA (linear_fwd, the dX pass of linear_bwd, the chain kernel): bitwise a k-ordered fmaf chain, k
+    roundings, the bias one more; slack 1  ->  k + 2."""
+    return float(k + 2)
+
+
+def _z(x):
+    return None if x is None else x.double()
+
+
+def head_linear(h, eh, w, b=None, extra=0):
+    """z = h w^T + b and its error bound: c(k + extra) u (|h| |w|^T + |b|) + eh |w|^T.  ``extra``: further products the
+    kernel sums into the same entry (e.g. a per-ray part)."""
+    w = w.detach().double()
+    aw = w.abs()
+    z = h @ w.T
+    a = h.abs() @ aw.T
+    if b is not None:
+        b = b.detach().double()
+        z, a = z + b, a + b.abs()
+    e = c_head_bf16x3(w.shape[1] + extra) * U * a
+    if eh is not None:
+        e = e + eh @ aw.T
+    return z, e
+
+
+def head_relu(z, ez, mask=None):
+    """ReLU with the product's own mask (its saved activations > 0) or, without one, the fp64 mask plus the units whose
+    pre-activation lies within its error bound of 0 (``amb``: either branch is correct there).  -> a, ea, mask, amb"""
+    if mask is None:
+        mask = z > 0
+        amb = z.abs() <= ez
+    else:
+        mask = mask.bool()
+        amb = torch.zeros_like(mask)
+    return z * mask, ez * (mask | amb), mask, amb
+
+
+def head_relu_bwd(d, ed, mask, amb):
+    """d relu: d * mask; an ambiguous unit may take the other branch: its whole |d| is error."""
+    return d * mask, ed * (mask | amb) + d.abs() * amb
+
+
+def head_sigmoid(z, ez):
+    y = torch.sigmoid(z)
+    return y, 0.25 * ez + C_SIG * U * y.abs()
+
+
+def head_sigmoid_bwd(go, y, ey):
+    """go y (1 - y) from the kernel's own (inexact) y: |go| |1 - 2 y| ey, and three roundings."""
+    d = go * y * (1 - y)
+    return d, go.abs() * (1 - 2 * y).abs() * ey + 3 * U * d.abs()
+
+
+def head_trunc_exp(f0, ef0):
+    """density exp(f0 - 1) and its bound: value x error of f0, plus C_EXP u of the value (inf past fp32 stays inf)."""
+    y = torch.exp(f0 - 1)
+    return y, y * ef0 + C_EXP * U * y
+
+
+def head_trunc_exp_bwd(gd, f0, ef0):
+    """side gradient gd exp(min(f0 - 1, 15)) and its bound (exp's own error and the product's rounding; f0's error
+    only below the clamp)."""
+    v = torch.exp(torch.clamp(f0 - 1, max=15.0))
+    s = gd * v
+    return s, gd.abs() * v * (ef0 * (f0 - 1 < 15) + C_EXP * U) + U * s.abs()
+
+
+def head_linear_bwd(d, ed, w, h, eh, dx_terms=None):
+    """Gradients of z = h w^T + b for dz = d (error ed), h with error eh: {dW, db, dx} -> (value, bound).  dW and db sum
+    over every row (c of the row count: any reduction structure); dx over the outputs (``dx_terms`` overrides the count
+    when the kernel sums further products into the same entry)."""
+    w = w.detach().double()
+    aw = w.abs()
+    M = d.shape[0]
+    ad, ah = d.abs(), h.abs()
+    out = {}
+    ew = c_head_bf16x3(M) * U * (ad.T @ ah) + ed.T @ ah
+    if eh is not None:
+        ew = ew + ad.T @ eh
+    out["dW"] = (d.T @ h, ew)
+    out["db"] = (d.sum(0), c_head_bf16x3(M) * U * ad.sum(0) + ed.sum(0))
+    out["dx"] = (d @ w, c_head_bf16x3(dx_terms or w.shape[0]) * U * (ad @ aw) + ed @ aw)
+    return out
+
+
+def assert_head_bound(got, ref, err, what: str, report: dict = None) -> float:
+    """|got - ref| <= err entry by entry (err from the head_* propagation; err = 0 -> exactly equal)."""
+    g = got.detach().double().cpu().numpy()
+    r = ref.detach().double().cpu().numpy()
+    e = err.detach().double().cpu().numpy()
+    return assert_bound(g, r, e / U, 1.0, what, report=report)

@@ -35,6 +35,9 @@ def test_base_mlp(hip_lib, L, Fe, NG, N):
     ((f_ref * gf.double()).sum() + (d_ref * gd.double()).sum()).backward()
     for name, a, b in zip(("denc", "dW0", "db0", "dW1", "db1"), t, r):
         _close(name, a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
+    neck_bound(f"base_mlp L{L}F{Fe}NG{NG}N{N}", x.detach(), W0, b0, W1, b1, gf.double(), gd.double(),
+               {"feats": feats, "density": dens, "dx": _lm_rows(t[0].grad, N), "dW0": t[1].grad, "db0": t[2].grad, "dW1": t[3].grad,
+                "db1": t[4].grad})
     # only one of the two outputs carries gradient
     t2 = [v.detach().clone().requires_grad_(True) for v in t]
     _, dens2 = fused.base_mlp(*t2)
@@ -79,6 +82,13 @@ def test_neck_register_resident(hip_lib, monkeypatch, L, Fe, NG, N, which, fused
     loss.backward(); loss_ref.backward()
     for name, a, b in zip(("denc", "dW0", "db0", "dW1", "db1"), t, r):
         _close(name, a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
+    z = torch.zeros(N, 64, dtype=torch.float64)
+    gfeat = torch.cat([gg.double() if which in ("all", "geo") else z, gs.double() if which in ("all", "sem") else z], 1)[:, :NG]
+    feats = geo if sem is None else torch.cat([geo, sem], 1)
+    neck_bound(f"neck L{L}F{Fe}NG{NG}N{N} {which} fusedw={fusedw}", x.detach(), W0, b0, W1, b1, gfeat,
+               gd.double() if which in ("all", "dens") else torch.zeros(N, dtype=torch.float64),
+               {"feats": feats, "density": dens, "dx": _lm_rows(t[0].grad, N), "dW0": t[1].grad, "db0": t[2].grad, "dW1": t[3].grad,
+                "db1": t[4].grad})
 
 
 @pytest.mark.parametrize("fusedw", [True, False])  # weight gradients inside the backward kernel (L F <= 16) / separate passes
@@ -104,6 +114,9 @@ def test_density_mlp(hip_lib, monkeypatch, L, N, Fe, fusedw):
         _close(name, a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
     with torch.no_grad():  # inference path: no activations saved
         _close("density_nograd", fused.density_mlp(*[v.detach() for v in t]), d_ref)
+    neck_bound(f"density_mlp L{L_rows}F{Fe}N{N} fusedw={fusedw}", enc.double().permute(1, 0, 2).reshape(N, L), W0, b0, W1, b1,
+               torch.zeros(N, 1, dtype=torch.float64), gd.double(),
+               {"density": dens, "dx": _lm_rows(t[0].grad, N), "dW0": t[1].grad, "db0": t[2].grad, "dW1": t[3].grad, "db1": t[4].grad})
 
 
 # weight gradients: all inside the backward kernel, only the output layer's
@@ -143,6 +156,9 @@ def test_rgb_head(hip_lib, monkeypatch, R, S, Kh, NG, ld, fusedw):
     _close("dfeats", fd.grad, f64.grad, rtol=2e-4, scale_atol=5e-5)
     for i, (a, b) in enumerate(zip(wd, w64)):
         _close(f"dW{i}", a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
+    got = {"out": rgb, "dhray": hd.grad, "dgeo": fd.grad[:, :NG]}
+    got.update({f"{k}{i}": wd[2 * i + j].grad for i in range(3) for j, k in enumerate(("dW", "db"))})
+    skip3_bound(f"rgb_head R{R}S{S}Kh{Kh} {fusedw}", inp.detach(), Ws, go.double(), True, got, per_ray=S, kh=Kh)
 
 
 @pytest.mark.parametrize("R,S,Kh,ld", [(16, 64, 49, 64), (5, 16, 49, 128), (1031, 32, 49, 64), (4100, 128, 49, 64), (2, 96, 17, 192), (1, 16, 49, 64)])
@@ -272,6 +288,8 @@ def test_skip_mlp3(hip_lib, N, K0, act):
     assert bad_rows <= max(1, N // 4096), f"dx: {bad_rows} rows differ"
     for name, a, b in list(zip(("dx", "dW0", "db0", "dW1", "db1", "dW2", "db2"), t, r))[1:]:
         _close(name, a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
+    skip3_bound(f"skip_mlp3 N{N}K{K0} {act}", r[0].detach(), vals[1:], w.double(), act == "sigmoid",
+                dict(zip(("out", "dx", "dW0", "db0", "dW1", "db1", "dW2", "db2"), [out] + [v.grad for v in t])))
 
 
 @pytest.fixture(params=[True, False], ids=["fusedw", "streamedw"])
@@ -310,6 +328,10 @@ def test_seq_mlp(hip_lib, dims, sig, N, rmlp_wgrad_mode):
     (out * w.to(dev)).sum().backward(); (ref * w.double()).sum().backward()
     for i, (a, b) in enumerate(zip(t, r)):
         _close(f"grad{i}", a.grad, b.grad, rtol=2e-4, scale_atol=5e-5)
+    got = {"out": out, "dx": t[0].grad}
+    got.update({f"dW{i}": t[1 + i].grad for i in range(n)})
+    got.update({f"db{i}": t[1 + n + i].grad for i in range(n)})
+    stack_bound(f"seq_mlp {dims} N{N} fusedw={rmlp_wgrad_mode}", r[0].detach(), Ws, Bs, sig, w.double(), got)
 
 
 @pytest.mark.parametrize("L,F,dims,N", [(10, 4, (64, 64, 6), 1000), (10, 4, (64, 6), 333), (4, 4, (64, 64, 64), 50), (16, 4, (64, 64, 3), 4099),
@@ -445,3 +467,99 @@ def test_field_forward_rides_along(hip_lib, L, Fe, R, S):
         other = [w.clone() for w in ph]
         rgb = fused.rgb_head(hray, geo, S, *other)
     assert rgb.data_ptr() != rider.out.data_ptr() and torch.equal(rgb, rider.out)
+
+
+# ------------------------------------------------------------------------------------------ per-entry bounds (tests/_bounds.py)
+def _lm_rows(t, N):
+    """level-major [L, N, F] -> row-major [N, L F]"""
+    return t.permute(1, 0, 2).reshape(N, -1)
+
+
+def neck_bound(tag, x, W0, b0, W1, b1, gfeat, gd, got: dict, masks=None):
+    """Per-entry bounds of the neck / base MLP / density MLP: x [N, K0] fp64, gfeat [N, NG] and gd [N] the output gradients (fp64,
+    zero where an output carries none).  got: feats / density / dx / dW0 / db0 / dW1 / db1 of the product (missing keys skipped)."""
+    from tests._bounds import (U, assert_head_bound, head_linear, head_linear_bwd, head_relu, head_relu_bwd, head_trunc_exp,
+                               head_trunc_exp_bwd)
+    z0, e0 = head_linear(x, None, W0, b0)
+    h, eh, m, amb = head_relu(z0, e0, masks)
+    f, ef = head_linear(h, eh, W1, b1)
+    dens, edens = head_trunc_exp(f[:, 0], ef[:, 0])
+    d, ed = gfeat.clone(), torch.zeros_like(gfeat)
+    s, es = head_trunc_exp_bwd(gd, f[:, 0], ef[:, 0])
+    d[:, 0] = d[:, 0] + s
+    ed[:, 0] = es + U * d[:, 0].abs() * (gfeat[:, 0] != 0)   # the side gradient joins column 0: one addition
+    g1 = head_linear_bwd(d, ed, W1, h, eh)
+    dh, edh = head_relu_bwd(*g1["dx"], m, amb)
+    g0 = head_linear_bwd(dh, edh, W0, x, None)
+    want = {"feats": (f[:, :got["feats"].shape[1]] if "feats" in got else None, ef), "density": (dens, edens), "dx": g0["dx"],
+            "dW0": g0["dW"], "db0": g0["db"], "dW1": g1["dW"], "db1": g1["db"]}
+    for k, v in got.items():
+        ref, err = want[k]
+        if k == "feats":
+            ref, err = f[:, :v.shape[1]], ef[:, :v.shape[1]]
+        assert_head_bound(v, ref, err, f"{tag} {k}")
+
+
+def skip3_bound(tag, x, Ws, go, sigmoid: bool, got: dict, per_ray: int = 0, kh: int = 0):
+    """Per-entry bounds of the 3-layer skip head (rgb head: x = [hray per sample | geo], per_ray = S samples per ray, kh = hray
+    width; skip_mlp3 / sky head: per_ray = 0).  got: out / dx (or dhray + dgeo) / dW0..db2 of the product."""
+    from tests._bounds import (U, assert_head_bound, c_head_bf16x3, head_linear, head_linear_bwd, head_relu, head_relu_bwd,
+                               head_sigmoid, head_sigmoid_bwd)
+    W0, b0, W1, b1, W2, b2 = [w.detach().double() for w in Ws]
+    H = W0.shape[0]
+    z0, e0 = head_linear(x, None, W0, b0)
+    a1, ea1, m1, amb1 = head_relu(z0, e0)
+    c = torch.cat([a1, x], 1)
+    ec = torch.cat([ea1, torch.zeros_like(x)], 1)
+    z1, e1 = head_linear(c, ec, W1, b1)
+    a2, ea2, m2, amb2 = head_relu(z1, e1)
+    z2, e2 = head_linear(a2, ea2, W2, b2)
+    out, eo = head_sigmoid(z2, e2) if sigmoid else (z2, e2)
+    d2, ed2 = head_sigmoid_bwd(go, out, eo) if sigmoid else (go, torch.zeros_like(go))
+    g2 = head_linear_bwd(d2, ed2, W2, a2, ea2)
+    da2, eda2 = head_relu_bwd(*g2["dx"], m2, amb2)
+    g1 = head_linear_bwd(da2, eda2, W1, c, ec)
+    dc, edc = g1["dx"]
+    da1, eda1 = head_relu_bwd(dc[:, :H], edc[:, :H], m1, amb1)
+    g0 = head_linear_bwd(da1, eda1, W0, x, None)
+    W1x = W1[:, H:]
+    # d input: both layers' products may meet in one sum (2 H terms per sample; S samples more per ray for dhray)
+    adx = da1.abs() @ W0.abs() + da2.abs() @ W1x.abs()
+    pdx = eda1 @ W0.abs() + eda2 @ W1x.abs()
+    dx = g0["dx"][0] + dc[:, H:]
+    want = {"out": (out, eo), "dW0": g0["dW"], "db0": g0["db"], "dW1": g1["dW"], "db1": g1["db"], "dW2": g2["dW"], "db2": g2["db"]}
+    if per_ray:
+        R = x.shape[0] // per_ray
+        want["dhray"] = (dx[:, :kh].reshape(R, per_ray, kh).sum(1),
+                         (c_head_bf16x3(2 * H * per_ray) * U * adx[:, :kh] + pdx[:, :kh]).reshape(R, per_ray, kh).sum(1))
+        want["dgeo"] = (dx[:, kh:], c_head_bf16x3(2 * H) * U * adx[:, kh:] + pdx[:, kh:])
+    else:
+        want["dx"] = (dx, c_head_bf16x3(2 * H) * U * adx + pdx)
+    for k, v in got.items():
+        assert_head_bound(v, *want[k], f"{tag} {k}")
+
+
+def stack_bound(tag, x, Ws, Bs, sigmoid: bool, go, got: dict, masks=None):
+    """Per-entry bounds of Linear-ReLU-...-Linear[-Sigmoid] (seq_mlp / seq_mlp_lm).  got: out / dx / dW<i> / db<i>."""
+    from tests._bounds import assert_head_bound, head_linear, head_linear_bwd, head_relu, head_relu_bwd, head_sigmoid, head_sigmoid_bwd
+    n = len(Ws)
+    h, eh, hs, rel = x, None, [], []
+    for i in range(n):
+        hs.append((h, eh))
+        z, ez = head_linear(h, eh, Ws[i], Bs[i])
+        if i + 1 < n:
+            h, eh, m, amb = head_relu(z, ez, None if masks is None else masks[i])
+            rel.append((m, amb))
+        else:
+            h, eh = head_sigmoid(z, ez) if sigmoid else (z, ez)
+    want = {"out": (h, eh)}
+    d, ed = head_sigmoid_bwd(go, h, eh) if sigmoid else (go, torch.zeros_like(go))
+    for i in reversed(range(n)):
+        g = head_linear_bwd(d, ed, Ws[i], *hs[i])
+        want[f"dW{i}"], want[f"db{i}"] = g["dW"], g["db"]
+        d, ed = g["dx"]
+        if i > 0:
+            d, ed = head_relu_bwd(d, ed, *rel[i - 1])
+    want["dx"] = (d, ed)
+    for k, v in got.items():
+        assert_head_bound(v, *want[k], f"{tag} {k}")

@@ -133,6 +133,10 @@ SIGNATURES = {
     "emer_buffer_to_pixels": [_P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, c_uint64, _P, _P, _P, _P],
     "emer_gen_rays": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "emer_gather_pixel_extras": [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P],
+    "emer_render_rays_lowres": [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P, c_int32,
+                                _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "emer_pixel_error_image": [_P, _P, _P, c_int64, _P, _P, _P],
+    "emer_pixel_error_normalise": [_P, c_int64, _P, c_int32, _P],
     "emer_ssim": [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P],
     "emer_sq_err_sums": [_P, _P, _P, c_int64, c_int32, _P, _P, _P],
     "emer_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_int32, _P],

@@ -15,6 +15,9 @@
 //     histograms, state in device memory: no host round trip), then one compaction pass emits the winners.  Keys are
 //     recomputed from the generator in every pass instead of being stored (the weights are read 4 times = 4 x 31 MB for
 //     200 images at 160 x 240: ~25 us at HBM speed).
+//   * emer_render_rays_lowres: get_render_rays at a downscale factor (:733-846) -- antialiased bicubic colours, nearest
+//     masks, rays of the scaled camera, features -- one launch per image.
+//   * emer_pixel_error_image / emer_pixel_error_normalise: update_pixel_error_maps (:491-517) on the device, in place.
 #include "common.h"
 
 namespace emer {
@@ -224,6 +227,142 @@ __global__ __launch_bounds__(256) void pixel_extras_kernel(const int64_t *__rest
     }
 }
 
+// ------------------------------------------------------------------------------- low-resolution render rays
+// get_render_rays at a downscale factor s != 1 (pixel_source.py:733-846): ONE launch per image, one workgroup per output
+// row.  Colours are torch's interpolate(mode="bicubic", antialias=True): a separable filter whose per-axis windows and
+// normalised weights come as tables (built once per factor by the host in double precision and rounded to fp32 once, so a
+// weight carries one rounding).  The workgroup first applies the row's vertical weights to the source rows it covers --
+// work items stride over x * 3 + c, so every source row is read coalesced -- and leaves the W * 3 partial sums in LDS; then
+// one work item per output (x, c) applies that column's horizontal weights to them.  Each sum is one serial fma chain
+// in registers: no atomics.  Masks are torch's mode="nearest" (source index floor(float(i) * float(1 / s))), the rays are
+// gen_rays_kernel's arithmetic on the w x h grid with the intrinsics scaled by float(s), features are get_features' lookup
+// with the map's scale divided by s.
+struct LowresArgs {
+    const float *images, *sky_masks, *dynamic_masks, *features;   // [n_imgs][H][W][3] | [n_imgs][H][W] x2 | [n_imgs][Hf][Wf][E]; each may be null
+    const float *c2w, *intrinsics, *timestamps;                   // timestamps may be null
+    const int64_t *cam_ids;                                       // may be null
+    const int32_t *ymin, *ysize; const float *wy;                 // [h], [h], [h][ky]
+    const int32_t *xmin, *xsize; const float *wx;                 // [w], [w], [w][kx]
+    int64_t img;
+    int32_t H, W, h, w, ky, kx, Hf, Wf, E;
+    float s, inv_s, feat_scale_y, feat_scale_x;
+    float *origins, *viewdirs, *direction_norm, *pixel_coords, *pixels, *sky, *dyn, *feat, *ray_t;
+    int64_t *ray_img, *ray_cam;
+};
+
+__global__ __launch_bounds__(256) void render_rays_lowres_kernel(const LowresArgs a) {
+    extern __shared__ float col[];   // [W * 3]: this output row's vertically filtered source row
+    const int32_t oy = blockIdx.x, tid = threadIdx.x;
+    if (a.images) {
+        const int32_t row_len = a.W * 3;
+        int32_t y0 = a.ymin[oy], ny = a.ysize[oy];
+        y0 = y0 < 0 ? 0 : (y0 > a.H ? a.H : y0);                     // (tables are validated by the host; never read outside the image regardless)
+        ny = ny < 0 ? 0 : (ny > a.ky ? a.ky : ny);
+        if (ny > a.H - y0) ny = a.H - y0;
+        const float *src = a.images + ((int64_t)a.img * a.H + y0) * row_len;
+        const float *wy = a.wy + (int64_t)oy * a.ky;
+        for (int32_t e = tid; e < row_len; e += 256) {
+            float acc = 0.0f;
+            for (int32_t j = 0; j < ny; ++j) acc = fmaf(wy[j], src[(int64_t)j * row_len + e], acc);
+            col[e] = acc;
+        }
+        __syncthreads();
+        for (int32_t o = tid; o < a.w * 3; o += 256) {
+            const int32_t ox = o / 3, c = o - ox * 3;
+            int32_t x0 = a.xmin[ox], nx = a.xsize[ox];
+            x0 = x0 < 0 ? 0 : (x0 > a.W ? a.W : x0);
+            nx = nx < 0 ? 0 : (nx > a.kx ? a.kx : nx);
+            if (nx > a.W - x0) nx = a.W - x0;
+            const float *wx = a.wx + (int64_t)ox * a.kx;
+            float acc = 0.0f;
+            for (int32_t j = 0; j < nx; ++j) acc = fmaf(wx[j], col[(x0 + j) * 3 + c], acc);
+            a.pixels[((int64_t)oy * a.w + ox) * 3 + c] = acc;
+        }
+    }
+    const float *K = a.intrinsics + a.img * 9, *M = a.c2w + a.img * 16;
+    // intrinsics * s with [2][2] reset to 1 (:827-828); the products are rounded on their own, as torch rounds them
+    const float fx = __fmul_rn(K[0], a.s), cx = __fmul_rn(K[2], a.s), fy = __fmul_rn(K[4], a.s), cy = __fmul_rn(K[5], a.s);
+    int32_t sy = (int32_t)floorf((float)oy * a.inv_s);
+    sy = sy > a.H - 1 ? a.H - 1 : sy;
+    for (int32_t ox = tid; ox < a.w; ox += 256) {
+        const int64_t i = (int64_t)oy * a.w + ox;
+        const float cd[3] = {((float)ox - cx + 0.5f) / fx, ((float)oy - cy + 0.5f) / fy, 1.0f};
+        float d[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d[r] = (cd[0] * M[r * 4 + 0] + cd[1] * M[r * 4 + 1]) + cd[2] * M[r * 4 + 2];
+        const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            a.origins[i * 3 + r] = M[r * 4 + 3];
+            a.viewdirs[i * 3 + r] = d[r] / (nrm + 1e-8f);
+        }
+        a.direction_norm[i] = nrm;
+        a.pixel_coords[i * 2 + 0] = (float)oy / (float)a.h;
+        a.pixel_coords[i * 2 + 1] = (float)ox / (float)a.w;
+        int32_t sx = (int32_t)floorf((float)ox * a.inv_s);
+        sx = sx > a.W - 1 ? a.W - 1 : sx;
+        const int64_t pix = ((int64_t)a.img * a.H + sy) * a.W + sx;
+        if (a.sky_masks) a.sky[i] = a.sky_masks[pix];
+        if (a.dynamic_masks) a.dyn[i] = a.dynamic_masks[pix];
+        if (a.timestamps) a.ray_t[i] = a.timestamps[a.img];
+        if (a.cam_ids) a.ray_cam[i] = a.cam_ids[a.img];
+        a.ray_img[i] = a.img;
+    }
+    if (a.features) {
+        int64_t fr = (int64_t)((float)oy * a.feat_scale_y);
+        fr = fr < 0 ? 0 : (fr > a.Hf - 1 ? a.Hf - 1 : fr);
+        for (int32_t o = tid; o < a.w * a.E; o += 256) {
+            const int32_t ox = o / a.E, e = o - ox * a.E;
+            int64_t fc = (int64_t)((float)ox * a.feat_scale_x);
+            fc = fc < 0 ? 0 : (fc > a.Wf - 1 ? a.Wf - 1 : fc);
+            a.feat[((int64_t)oy * a.w + ox) * a.E + e] = a.features[((a.img * a.Hf + fr) * a.Wf + fc) * a.E + e];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------ error-buffer refresh
+// update_pixel_error_maps (:491-517) on the device, in place.  pixel_error_image_kernel: ONE workgroup writes an image's
+// row of the buffer, err = mean_c |gt - pred| (x 5 where the dynamic opacity exceeds 0.1), and leaves the row's (min, max)
+// in extrema[2 * img ..]: wave shuffles, then LDS across the 16 waves -- no atomics.  pixel_error_normalise_kernel: every
+// workgroup reduces the per-image extrema itself (a few hundred pairs) and normalises its share of the buffer.
+__device__ __forceinline__ void block_min_max(float &lo, float &hi, float *red /* [32] */) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, off, kWave));
+        hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
+    }
+    const int wave = threadIdx.x / kWave, n_waves = blockDim.x / kWave;
+    if (threadIdx.x % kWave == 0) { red[wave] = lo; red[16 + wave] = hi; }
+    __syncthreads();
+    lo = red[0]; hi = red[16];
+    for (int k = 1; k < n_waves; ++k) { lo = fminf(lo, red[k]); hi = fmaxf(hi, red[16 + k]); }
+}
+
+__global__ __launch_bounds__(1024) void pixel_error_image_kernel(const float *__restrict__ pred, const float *__restrict__ gt,
+                                                                 const float *__restrict__ dyn_opacity, int64_t n_cells,
+                                                                 float *__restrict__ err, float *__restrict__ extrema) {
+    __shared__ float red[32];
+    float lo = INFINITY, hi = -INFINITY;
+    for (int64_t i = threadIdx.x; i < n_cells; i += 1024) {
+        float e = ((fabsf(gt[i * 3 + 0] - pred[i * 3 + 0]) + fabsf(gt[i * 3 + 1] - pred[i * 3 + 1])) + fabsf(gt[i * 3 + 2] - pred[i * 3 + 2])) / 3.0f;
+        if (dyn_opacity && dyn_opacity[i] > 0.1f) e *= 5.0f;
+        err[i] = e;
+        lo = fminf(lo, e); hi = fmaxf(hi, e);
+    }
+    block_min_max(lo, hi, red);
+    if (threadIdx.x == 0) { extrema[0] = lo; extrema[1] = hi; }
+}
+
+__global__ __launch_bounds__(256) void pixel_error_normalise_kernel(float *__restrict__ maps, int64_t n, const float *__restrict__ extrema,
+                                                                    int32_t n_imgs) {
+    __shared__ float red[32];
+    float lo = INFINITY, hi = -INFINITY;
+    for (int32_t k = threadIdx.x; k < n_imgs; k += 256) { lo = fminf(lo, extrema[2 * k]); hi = fmaxf(hi, extrema[2 * k + 1]); }
+    block_min_max(lo, hi, red);
+    const float range = hi - lo;   // 0 when every cell is equal: 0 / 0 = NaN, as the reference's division gives
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) maps[i] = (maps[i] - lo) / range;
+}
+
 }  // namespace emer
 
 using namespace emer;
@@ -319,4 +458,50 @@ extern "C" int emer_buffer_to_pixels(const int64_t *flat, int64_t n, int32_t buf
     hipLaunchKernelGGL(buffer_to_pixels_kernel, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), flat, n, buffer_height,
                        buffer_width, downscale, candidates, height, width, seed_word, salt, img_idx, y, x);
     return check_launch("buffer_to_pixels");
+}
+
+extern "C" int emer_render_rays_lowres(int64_t img_idx, const float *cam_to_worlds, const float *intrinsics, const float *images,
+                                       const float *sky_masks, const float *dynamic_masks, const float *features,
+                                       const float *timestamps, const int64_t *cam_ids, int32_t height, int32_t width,
+                                       int32_t out_height, int32_t out_width, float scale, float inv_scale, const int32_t *ymin,
+                                       const int32_t *ysize, const float *wy, int32_t ky, const int32_t *xmin, const int32_t *xsize,
+                                       const float *wx, int32_t kx, int32_t feat_height, int32_t feat_width, int32_t feat_dim,
+                                       float feat_scale_y, float feat_scale_x, float *origins, float *viewdirs, float *direction_norm,
+                                       float *pixel_coords, float *pixels, float *sky, float *dyn, float *out_features,
+                                       float *ray_timestamps, int64_t *ray_img_idx, int64_t *ray_cam_ids, void *stream) {
+    EMER_REQUIRE(img_idx >= 0 && height >= 1 && width >= 1 && out_height >= 1 && out_width >= 1 && out_height <= height && out_width <= width,
+                 "render_rays_lowres: need 1 <= out size <= size");
+    EMER_REQUIRE(scale > 0.0f && inv_scale > 0.0f, "render_rays_lowres: need a positive scale");
+    EMER_REQUIRE(cam_to_worlds && intrinsics && origins && viewdirs && direction_norm && pixel_coords && ray_img_idx,
+                 "render_rays_lowres: null pointer");
+    EMER_REQUIRE((!images || (pixels && ymin && ysize && wy && xmin && xsize && wx && ky >= 1 && kx >= 1)) && (!sky_masks || sky) &&
+                 (!dynamic_masks || dyn) && (!timestamps || ray_timestamps) && (!cam_ids || ray_cam_ids) && (!features || out_features),
+                 "render_rays_lowres: a dataset tensor was given without its output buffer or filter tables");
+    EMER_REQUIRE(!features || (feat_height >= 1 && feat_width >= 1 && feat_dim >= 1), "render_rays_lowres: bad feature-map sizes");
+    const size_t lds = images ? (size_t)width * 3 * sizeof(float) : 0;
+    EMER_REQUIRE(lds <= 48 * 1024, "render_rays_lowres: images wider than 4096 pixels are not supported (row buffer in LDS)");
+    LowresArgs a{images, sky_masks, dynamic_masks, features, cam_to_worlds, intrinsics, timestamps, cam_ids, ymin, ysize, wy, xmin, xsize, wx,
+                 img_idx, height, width, out_height, out_width, ky, kx, feat_height, feat_width, feat_dim, scale, inv_scale, feat_scale_y,
+                 feat_scale_x, origins, viewdirs, direction_norm, pixel_coords, pixels, sky, dyn, out_features, ray_timestamps, ray_img_idx,
+                 ray_cam_ids};
+    hipLaunchKernelGGL(render_rays_lowres_kernel, dim3((uint32_t)out_height), dim3(256), lds, as_stream(stream), a);
+    return check_launch("render_rays_lowres");
+}
+
+extern "C" int emer_pixel_error_image(const float *pred_rgb, const float *gt_rgb, const float *dynamic_opacity, int64_t n_cells,
+                                      float *error_row, float *extrema, void *stream) {
+    EMER_REQUIRE(n_cells >= 1, "pixel_error_image: need at least one cell");
+    EMER_REQUIRE(pred_rgb && gt_rgb && error_row && extrema, "pixel_error_image: null pointer");
+    hipLaunchKernelGGL(pixel_error_image_kernel, dim3(1), dim3(1024), 0, as_stream(stream), pred_rgb, gt_rgb, dynamic_opacity, n_cells,
+                       error_row, extrema);
+    return check_launch("pixel_error_image");
+}
+
+extern "C" int emer_pixel_error_normalise(float *error_maps, int64_t n_cells, const float *extrema, int32_t n_imgs, void *stream) {
+    EMER_REQUIRE(n_cells >= 1 && n_imgs >= 1, "pixel_error_normalise: need at least one cell and one image");
+    EMER_REQUIRE(error_maps && extrema, "pixel_error_normalise: null pointer");
+    int64_t blocks = ceil_div(n_cells, 256 * 4);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(pixel_error_normalise_kernel, dim3((uint32_t)blocks), dim3(256), 0, as_stream(stream), error_maps, n_cells, extrema, n_imgs);
+    return check_launch("pixel_error_normalise");
 }

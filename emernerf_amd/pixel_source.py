@@ -2,21 +2,25 @@
 
 Mirrors the ray-facing part of the reference's ``ScenePixelSource`` (datasets/base/pixel_source.py): ``get_rays``
 (:39-76), ``sample_uniform_rays`` (:622-668), ``sample_important_rays`` (:564-620), ``get_train_rays`` (:670-731),
-``get_render_rays`` (:733-826, full resolution), ``build_pixel_error_buffer`` / ``update_pixel_error_maps`` (:462-517).
+``get_render_rays`` (:733-846, at any ``downscale_factor``, :955-976), ``build_pixel_error_buffer`` /
+``update_pixel_error_maps`` (:462-517) and its on-device form ``accumulate_pixel_error`` / ``finish_pixel_error_maps``.
 Loading images / poses from disk (the dataset classes proper) stays out of scope: the constructor takes the tensors the
 reference's loaders produce.
 
 Every per-batch operation is a HIP kernel (csrc/rays.hip): one launch for uniform pixels, a radix-select race for the
 error-buffer multinomial (no host round trip), one gather kernel for rays + colours + masks + timestamps, and (when the
-source has them) one more for the dynamic masks and the DINO feature rows (``get_features``, :439-468).  Random numbers
+source has them) one more for the dynamic masks and the DINO feature rows (``get_features``, :439-468); a low-resolution
+render image (antialiased bicubic colours, nearest masks, rays of the scaled camera, features) is one launch.  Random numbers
 come from a counter-based generator keyed by a seed word in device memory (``self.seed_word``), advanced by one tiny
 device op per batch, so a captured hipGraph replays with fresh rays.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -46,6 +50,34 @@ def get_rays(x: Tensor, y: Tensor, c2w: Tensor, intrinsic: Tensor) -> Tuple[Tens
         _lib.call("emer_gen_rays", _ptr(idx), _ptr(yi), _ptr(xi), _ptr(c2w), _ptr(K), None, None, None, None, n, 1, 1, _ptr(o), _ptr(d),
                   _ptr(nrm), None, None, None, None, None, _stream(o))
     return o, d, nrm
+
+
+def _cubic(x: np.ndarray, a: float = -0.5) -> np.ndarray:
+    """Keys' cubic convolution kernel (a = -0.5: torch's antialiased bicubic filter)."""
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
+                    np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
+
+
+def antialias_bicubic_tables(in_size: int, out_size: int, scale_factor: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One axis of torch's ``interpolate(scale_factor=s, mode="bicubic", antialias=True)`` for s <= 1 as tables: output i sums
+    the inputs xmin[i] .. xmin[i] + xsize[i] - 1 with the weights w[i, :xsize[i]] (zero beyond).  Support 2 / s, centre
+    (i + 0.5) / s, window [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), in_size)), tap weight
+    cubic((j - c + 0.5) * s) normalised over the window actually used (so image borders renormalise).  Computed in double
+    precision and rounded to float32 once: a weight the kernel reads carries a single rounding."""
+    inv = 1.0 / scale_factor
+    support = 2.0 * inv
+    k = int(math.ceil(support)) * 2 + 1
+    centre = (np.arange(out_size, dtype=np.float64) + 0.5) * inv
+    xmin = np.maximum((centre - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum((centre + support + 0.5).astype(np.int64), in_size)
+    xsize = xmax - xmin
+    j = np.arange(k, dtype=np.int64)[None, :]
+    w = _cubic((j + xmin[:, None] - centre[:, None] + 0.5) * scale_factor)
+    w = np.where(j < xsize[:, None], w, 0.0)
+    w = w / w.sum(axis=1, keepdims=True)
+    assert xsize.min() >= 1 and xsize.max() <= k and xmin.min() >= 0 and (xmin + xsize).max() <= in_size
+    return xmin.astype(np.int32), xsize.astype(np.int32), w.astype(np.float32)
 
 
 class PixelSource:
@@ -83,6 +115,24 @@ class PixelSource:
         self.seed_word = torch.tensor([seed], dtype=torch.int64, device=self.device)  # read by the kernels as uint64
         self._ws = torch.empty(4 + 2048, dtype=torch.int32, device=self.device)
         self._all = None
+        self._downscale_factor = self._old_downscale_factor = 1.0
+        self._resample_tables = None                  # (factor, device tables) of the low-resolution render path
+        self._error_extrema: Optional[Tensor] = None  # [n_imgs, 2] per-image (min, max) of the error-buffer refresh
+        self._error_rows_written: set = set()
+
+    # ---------------------------------------------------------------------------------- downscale factor (:955-976)
+    @property
+    def downscale_factor(self) -> float:
+        """Factor of ``get_render_rays`` (1.0: full resolution).  ``get_train_rays`` does not look at it (nor does the reference's)."""
+        return self._downscale_factor
+
+    def update_downscale_factor(self, downscale: float) -> None:
+        self._old_downscale_factor = self._downscale_factor
+        self._downscale_factor = downscale
+
+    def reset_downscale_factor(self) -> None:
+        """Back to the value before the last ``update_downscale_factor``."""
+        self._downscale_factor = self._old_downscale_factor
 
     # ------------------------------------------------------------------------------------ error buffer (:462-517)
     def build_pixel_error_buffer(self) -> None:
@@ -100,6 +150,49 @@ class PixelSource:
         if dynamic_opacities is not None:
             err = torch.where(dynamic_opacities.to(self.device).reshape(err.shape) > 0.1, err * 5, err)
         self.pixel_error_maps = ((err - err.min()) / (err.max() - err.min())).contiguous()
+        self.pixel_error_buffered = True
+
+    def accumulate_pixel_error(self, img_idx: int, pred_rgb: Tensor, gt_rgb: Tensor, dynamic_opacity: Optional[Tensor] = None) -> None:
+        """One image's share of ``update_pixel_error_maps`` on the device: mean_c |gt - pred| (x5 where the dynamic opacity
+        exceeds 0.1) written INTO the buffer's row ``img_idx`` -- the buffer keeps its storage, so a captured sampler graph
+        keeps reading it -- and the row's (min, max) left in a small device array for ``finish_pixel_error_maps``.  pred_rgb /
+        gt_rgb: [Hb, Wb, 3] (or [Hb * Wb, 3]) fp32 on the device at the buffer's resolution; one launch, no host transfer.
+        Between the first call of a refresh and ``finish_pixel_error_maps`` the buffer holds unnormalised rows."""
+        if self.pixel_error_maps is None:
+            return
+        _check_cuda(pred_rgb, gt_rgb, dynamic_opacity)
+        maps = self.pixel_error_maps
+        cells = maps.shape[1] * maps.shape[2]
+        if not 0 <= int(img_idx) < self.num_imgs:
+            raise IndexError(f"accumulate_pixel_error: image {img_idx} of {self.num_imgs}")
+        if pred_rgb.numel() != cells * 3 or gt_rgb.numel() != cells * 3 or (dynamic_opacity is not None and dynamic_opacity.numel() != cells):
+            raise ValueError(f"accumulate_pixel_error: expected {tuple(maps.shape[1:])} x 3 colours (and as many opacities), got "
+                             f"{tuple(pred_rgb.shape)}, {tuple(gt_rgb.shape)}" + ("" if dynamic_opacity is None else f", {tuple(dynamic_opacity.shape)}"))
+        assert maps.is_contiguous() and maps.dtype == torch.float32
+        pred, gt = pred_rgb.detach().float().contiguous(), gt_rgb.detach().float().contiguous()
+        opa = None if dynamic_opacity is None else dynamic_opacity.detach().float().contiguous()
+        if self._error_extrema is None:
+            self._error_extrema = torch.empty((self.num_imgs, 2), dtype=torch.float32, device=self.device)
+        row, ext = maps[int(img_idx)], self._error_extrema[int(img_idx)]
+        with torch.cuda.device(self.device):
+            _lib.call("emer_pixel_error_image", _ptr(pred), _ptr(gt), _ptr(opa), cells, _ptr(row), _ptr(ext), _stream(maps))
+        self._error_rows_written.add(int(img_idx))
+        self._support_cache = None    # a raw-pointer write does not bump the tensor's version counter
+
+    def finish_pixel_error_maps(self) -> None:
+        """Normalise the whole buffer to (e - min) / (max - min) in place, in one launch that also reduces the per-image
+        extrema.  Every image must have been given to ``accumulate_pixel_error`` since the last finish (the reference
+        normalises over the full set too).  max == min gives NaN in every cell, as the reference's division does."""
+        if self.pixel_error_maps is None:
+            return
+        missing = set(range(self.num_imgs)) - self._error_rows_written
+        if missing:
+            raise RuntimeError(f"finish_pixel_error_maps: {len(missing)} of {self.num_imgs} images were not accumulated (first: {min(missing)})")
+        maps = self.pixel_error_maps
+        with torch.cuda.device(self.device):
+            _lib.call("emer_pixel_error_normalise", _ptr(maps), maps.numel(), _ptr(self._error_extrema), self.num_imgs, _stream(maps))
+        self._error_rows_written = set()
+        self._support_cache = None
         self.pixel_error_buffered = True
 
     # ------------------------------------------------------------------------------------------------ sampling
@@ -214,8 +307,59 @@ class PixelSource:
         self._next_seed()
         return self._gather(img_idx, y, x)
 
+    def _lowres_tables(self, s: float):
+        if self._resample_tables is None or self._resample_tables[0] != s:
+            h, w = int(math.floor(self.HEIGHT * s)), int(math.floor(self.WIDTH * s))
+            if not (0 < s < 1.0 and h >= 1 and w >= 1):
+                raise ValueError(f"downscale_factor {s}: need 0 < factor <= 1 and at least one output pixel per axis")
+            ty, tx = antialias_bicubic_tables(self.HEIGHT, h, s), antialias_bicubic_tables(self.WIDTH, w, s)
+            dev_t = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (*ty, *tx))
+            self._resample_tables = (s, h, w, ty[2].shape[1], tx[2].shape[1], dev_t)
+        return self._resample_tables[1:]
+
+    def _render_rays_lowres(self, img_idx: int, s: float) -> Dict[str, Tensor]:
+        """:733-846 at a factor != 1 in one launch (csrc/rays.hip render_rays_lowres_kernel): [h, w] = floor([H, W] * s)."""
+        h, w, ky, kx, (ymin, ysize, wy, xmin, xsize, wx) = self._lowres_tables(s)
+        dev = self.device
+        if not 0 <= int(img_idx) < self.num_imgs:
+            raise IndexError(f"get_render_rays: image {img_idx} of {self.num_imgs}")
+        out = {"origins": torch.empty((h, w, 3), device=dev), "viewdirs": torch.empty((h, w, 3), device=dev),
+               "direction_norm": torch.empty((h, w, 1), device=dev), "pixel_coords": torch.empty((h, w, 2), device=dev)}
+        ts = torch.empty((h, w), device=dev) if self.normalized_timestamps is not None else None
+        img = torch.empty((h, w), dtype=torch.int64, device=dev)
+        cam = torch.empty((h, w), dtype=torch.int64, device=dev) if self.cam_ids is not None else None
+        pixels = torch.empty((h, w, 3), device=dev)
+        sky = torch.empty((h, w), device=dev) if self.sky_masks is not None else None
+        dyn = torch.empty((h, w), device=dev) if self.dynamic_masks is not None else None
+        feat, Hf, Wf, E, fsy, fsx = None, 0, 0, 0, 0.0, 0.0
+        if self.features is not None:
+            _, Hf, Wf, E = self.features.shape
+            fsy, fsx = self.featmap_downscale_factor[0] / s, self.featmap_downscale_factor[1] / s   # :803-806
+            feat = torch.empty((h, w, E), device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("emer_render_rays_lowres", int(img_idx), _ptr(self.cam_to_worlds), _ptr(self.intrinsics), _ptr(self.images),
+                      _ptr(self.sky_masks), _ptr(self.dynamic_masks), _ptr(self.features), _ptr(self.normalized_timestamps), _ptr(self.cam_ids),
+                      self.HEIGHT, self.WIDTH, h, w, s, 1.0 / s, _ptr(ymin), _ptr(ysize), _ptr(wy), ky, _ptr(xmin), _ptr(xsize), _ptr(wx), kx,
+                      Hf, Wf, E, fsy, fsx, _ptr(out["origins"]), _ptr(out["viewdirs"]), _ptr(out["direction_norm"]), _ptr(out["pixel_coords"]),
+                      _ptr(pixels), _ptr(sky), _ptr(dyn), _ptr(feat), _ptr(ts), _ptr(img), _ptr(cam), _stream(pixels))
+        if ts is not None:
+            out["normed_timestamps"] = ts
+        out["img_idx"] = img
+        if cam is not None:
+            out["cam_idx"] = cam
+        out["pixels"] = pixels
+        for k, v in (("sky_masks", sky), ("dynamic_masks", dyn), ("features", feat)):
+            if v is not None:
+                out[k] = v
+        return out
+
     def get_render_rays(self, img_idx: int) -> Dict[str, Tensor]:
-        """:733-826 at full resolution: every pixel of one image, image-shaped tensors (H, W, ...)."""
+        """:733-846: every pixel of one image, image-shaped tensors (H, W, ...).  At ``downscale_factor`` s != 1 the image is
+        [floor(H s), floor(W s)]: colours resampled as torch's antialiased bicubic ``interpolate`` does, masks by its nearest
+        mode, rays through the pixel centres of the camera with intrinsics * s, features looked up at the rescaled
+        coordinates -- one launch; at 1.0, the full-resolution gather."""
+        if self._downscale_factor != 1.0:
+            return self._render_rays_lowres(img_idx, float(self._downscale_factor))
         H, W, dev = self.HEIGHT, self.WIDTH, self.device
         if self._all is None:
             yy, xx = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")

@@ -9,7 +9,9 @@ What changed underneath: an image's rays come from ``PixelSource.get_render_rays
 image are rendered before any result leaves the GPU, an image's results leave it as ONE asynchronous transfer that overlaps
 the next image's rendering (the reference interleaves a blocking ``.cpu().numpy()`` per key with the rendering), and the
 metrics -- PSNR, SSIM (scikit-image's algorithm, csrc/metrics.hip), feature PSNR and their dynamic-mask variants -- are
-computed on the device and read back once after the loop.  Out of scope here: video encoding, DINO-feature PCA colouring.
+computed on the device and read back once after the loop.  ``cache_pixel_error_maps`` is the training loop's periodic
+refresh of the importance sampler's error buffer (train_emernerf.py:879-904): a low-resolution pass over the full set whose
+results never leave the GPU.  Out of scope here: video encoding, DINO-feature PCA colouring.
 """
 from __future__ import annotations
 
@@ -74,7 +76,10 @@ def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimato
                   proposal_networks: Optional[List[DensityField]] = None, compute_metrics: bool = False,
                   vis_indices: Optional[List[int]] = None, return_decomposition: bool = True) -> Dict[str, list]:
     """video_utils.py:50-106.  ``dataset``: anything with ``__len__`` / ``__getitem__`` returning image-shaped ray dicts
-    (``PixelSource`` here; the reference's SplitWrapper there)."""
+    (``PixelSource`` here; the reference's SplitWrapper there).  Nothing here or in ``render`` depends on the image size: with
+    ``PixelSource.update_downscale_factor(1 / k)`` set, the same loop is the reference's low-resolution preview pass
+    (train_emernerf.py:290-302) on [floor(H / k), floor(W / k)] images; previews smaller than 7 x 7 fall under ``render``'s
+    SSIM rule."""
     model.eval()
     for p in proposal_networks or []:
         p.eval()
@@ -96,6 +101,35 @@ def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimato
         logger.info(f"\tMasked SSIM: {results['masked_ssim']:.4f}")
         logger.info(f"\tMasked Feature PSNR: {results['masked_feat_psnr']:.4f}")
     return results
+
+
+def cache_pixel_error_maps(cfg, model: RadianceField, proposal_estimator: PropNetEstimator, pixel_source,
+                           proposal_networks: Optional[List[DensityField]] = None) -> None:
+    """train_emernerf.py:884-904: re-render every image at 1 / buffer_downscale of its size in eval mode and re-weight the
+    importance sampler with the result.  ``render_rays`` (chunked by cfg.render.render_chunk_size) leaves ``rgb`` and
+    ``dynamic_opacity`` on the device, where ``PixelSource.accumulate_pixel_error`` turns them and the resampled ground truth
+    into the image's row of the error buffer; ``finish_pixel_error_maps`` normalises the buffer in place.  No host transfer,
+    and the buffer keeps its storage.  The downscale factor is reset and every module's train / eval mode restored, also when
+    rendering raises.  A source without an error buffer (buffer_ratio == 0) is left alone, as in the reference."""
+    if pixel_source.pixel_error_maps is None:
+        return
+    modules = [m for m in (model, proposal_estimator, *(proposal_networks or [])) if m is not None]
+    modes = [m.training for m in modules]
+    for m in modules:
+        m.eval()
+    pixel_source.update_downscale_factor(1 / pixel_source.buffer_downscale)
+    try:
+        with torch.no_grad():
+            for i in range(len(pixel_source)):
+                data = pixel_source[i]
+                res = render_rays(radiance_field=model, proposal_estimator=proposal_estimator, proposal_networks=proposal_networks,
+                                  data_dict=data, cfg=cfg, return_decomposition=True)
+                pixel_source.accumulate_pixel_error(i, res["rgb"], data["pixels"], res.get("dynamic_opacity"))
+            pixel_source.finish_pixel_error_maps()
+    finally:
+        pixel_source.reset_downscale_factor()
+        for m, training in zip(modules, modes):
+            m.train(training)
 
 
 def render(dataset, render_func: Callable, model: Optional[RadianceField] = None, compute_metrics: bool = False,

@@ -747,6 +747,35 @@ int emer_gather_pixel_extras(const int64_t *img_idx, const int64_t *y, const int
                              int32_t feat_width, int32_t feat_dim, float scale_y, float scale_x, float *out_masks,
                              float *out_features, void *stream);
 
+/* get_render_rays of image img_idx at a downscale factor s != 1 (pixel_source.py:733-846), image-shaped
+ * [out_height][out_width][...] outputs, ONE launch (one workgroup per output row).  out size = floor(size * s).
+ * pixels: torch's interpolate(mode="bicubic", antialias=True) as a separable filter given by tables: output row y sums source
+ * rows ymin[y] .. ymin[y] + ysize[y] - 1 with the normalised weights wy[y * ky ..], columns likewise (xmin, xsize, wx, kx);
+ * the tables must stay inside the image (ymin >= 0, ymin + ysize <= height, ysize <= ky).  sky / dyn: mode="nearest", source
+ * index min((int)floorf((float)i * inv_scale), size - 1) per axis.  Rays: intrinsics * scale (fp32) with [2][2] = 1, then
+ * emer_gen_rays' arithmetic on the out_width x out_height grid; pixel_coords = (y / out_height, x / out_width).  Features:
+ * row ((int64)((float)y * feat_scale_y), (int64)((float)x * feat_scale_x)) with feat_scale = (Hf / H) / s.  ray_img_idx =
+ * img_idx, ray_timestamps / ray_cam_ids as emer_gen_rays.  images, sky_masks, dynamic_masks, features, timestamps and cam_ids
+ * may each be NULL (its output is then not written).  width <= 4096 (one source row of partial sums is kept in LDS). */
+int emer_render_rays_lowres(int64_t img_idx, const float *cam_to_worlds, const float *intrinsics, const float *images,
+                            const float *sky_masks, const float *dynamic_masks, const float *features,
+                            const float *timestamps, const int64_t *cam_ids, int32_t height, int32_t width,
+                            int32_t out_height, int32_t out_width, float scale, float inv_scale, const int32_t *ymin,
+                            const int32_t *ysize, const float *wy, int32_t ky, const int32_t *xmin, const int32_t *xsize,
+                            const float *wx, int32_t kx, int32_t feat_height, int32_t feat_width, int32_t feat_dim,
+                            float feat_scale_y, float feat_scale_x, float *origins, float *viewdirs, float *direction_norm,
+                            float *pixel_coords, float *pixels, float *sky, float *dyn, float *out_features,
+                            float *ray_timestamps, int64_t *ray_img_idx, int64_t *ray_cam_ids, void *stream);
+
+/* On-device refresh of the pixel error buffer (update_pixel_error_maps, pixel_source.py:491-517).
+ * emer_pixel_error_image: error_row[i] = mean_c |gt_rgb[i][c] - pred_rgb[i][c]| over n_cells cells ([n_cells][3] fp32), times 5
+ * where dynamic_opacity[i] > 0.1 (may be NULL); extrema[0..1] = (min, max) of the row.  One workgroup, no atomics.
+ * emer_pixel_error_normalise: error_maps[i] = (error_maps[i] - min) / (max - min) in place over n_cells cells, with min / max
+ * reduced over the n_imgs (min, max) pairs of extrema; max == min gives NaN, as the reference's division does. */
+int emer_pixel_error_image(const float *pred_rgb, const float *gt_rgb, const float *dynamic_opacity, int64_t n_cells,
+                           float *error_row, float *extrema, void *stream);
+int emer_pixel_error_normalise(float *error_maps, int64_t n_cells, const float *extrema, int32_t n_imgs, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics (radiance_fields/video_utils.py:206-247), results left on the device.
  * ---------------------------------------------------------------------------------------------- */

@@ -20,6 +20,7 @@
 //   5. the only tensor with a gradient is the proposal cdf (:213: wp = diff(prop_cdfs)), so the backward is local to
 //      the ray: d cdf_j = g_{j-1} - g_j with g = d term / d wp.  Written in the same launch.
 // Per-ray partial losses are reduced by a second, deterministic single-workgroup kernel (fixed summation order).
+// Tests: tests/_prop_probe.py (exact probes, numpy model); tests/test_prop_loss_bounds_cpu.py, tests/test_prop_loss_exact_gpu.py.
 #include "common.h"
 
 namespace emer {

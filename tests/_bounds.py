@@ -257,3 +257,165 @@ def assert_head_bound(got, ref, err, what: str, report: dict = None) -> float:
     r = ref.detach().double().cpu().numpy()
     e = err.detach().double().cpu().numpy()
     return assert_bound(g, r, e / U, 1.0, what, report=report)
+
+
+# ------------------------------------------------------------------------------------------- proposal-loss kernel
+# emer_prop_loss (csrc/proploss.hip).  Two regimes (tests/_prop_probe.py):
+#
+# Exact probes: everything up to the hinge argument d = max(w_s - w_p, 0) is exact, w_p = c_{j+1} - c_j too.  What follows
+# are correctly rounded fp32 operations (HIP's default fp32 division is correctly rounded), counted per result below.
+#
+# Realistic inputs: first-order propagation through the kernel's stages (``prop_aa_bound``), one rounding per addition
+# (a sum of k terms in any order puts each term through at most k - 1 roundings: it covers the kernel's chunked wave
+# scans and torch's sequential cumsum alike), abs-sums from the fp64 evaluation.
+
+C_PROP_DEN = 2.0   # den = fl(w_p + eps_f32) against w_p + eps: one rounding, and |eps_f32 - eps| <= u eps <= u den
+
+
+def c_prop_term(exact_wp: bool = True) -> float:
+    """One loss term d^2 / den relative to itself: d d (1), den (2, + 1 when w_p = c_{j+1} - c_j rounds), the division (1)."""
+    return 1.0 + C_PROP_DEN + (0.0 if exact_wp else 1.0) + 1.0
+
+
+def c_prop_G(exact_wp: bool = True) -> float:
+    """G = -2 d / den - d^2 / den^2 relative to itself (both quotients have the same sign: |G| is their sum):
+    q1 = fl(fl(-2 d) / den): -2 d exact, den e, the division 1                      -> (e + 1) u |q1|
+    q2 = fl(fl(d d) / fl(den den)): d d 1, den den 2 e + 1, the division 1          -> (2 e + 3) u |q2|
+    G = fl(q1 - q2): 1 more                                                         -> (2 e + 4) u |G|, e = 2 (3 inexact)."""
+    e = C_PROP_DEN + (0.0 if exact_wp else 1.0)
+    return 2.0 * e + 4.0
+
+
+def c_prop_grad(exact_wp: bool = True) -> float:
+    """d cdf_j = fl(fl(G_{j-1} - G_j) scale) against (|G_{j-1}| + |G_j|) scale: each G carries c_prop_G, the difference
+    and the product one rounding each (relative to |G_{j-1} - G_j| <= |G_{j-1}| + |G_j|), slack 1."""
+    return c_prop_G(exact_wp) + 2.0 + 1.0
+
+
+def c_prop_ray_loss(k: int, exact_wp: bool = True) -> float:
+    """Per-ray loss (all terms >= 0, so relative to the value itself): one term c_prop_term, ceil(k / 64) additions per
+    lane, the six steps of the wave sum, the product with scale, slack 1.  k: the intervals summed (m; n in pdf mode)."""
+    return c_prop_term(exact_wp) + float(-(-k // 64)) + 6.0 + 1.0 + 1.0
+
+
+C_PROP_TOTAL = 1.0  # the reduction kernel accumulates in double: one final rounding (2^-53 n below the slack: |.| <= u |sum|)
+
+
+def c_prop_pdf_grad(hits) -> np.ndarray:
+    """Mode 1, per proposal entry, against scale sum |g| over its hits: g = fl(fl(-2 d) / den) with w exact and den
+    one rounding + the constant (C_PROP_DEN) + the division (1) = 3; `hits` LDS atomics in any order (hits - 1 roundings,
+    each seeing at most the abs-sum; counted hits); the product with scale (1); slack 1."""
+    return np.asarray(hits, np.float64) + (C_PROP_DEN + 1.0) + 1.0 + 1.0
+
+
+def _prefix(a):
+    return np.cumsum(a)
+
+
+def prop_aa_bound(st: dict, scale: float) -> dict:
+    """First-order error bounds for mode 0 on arbitrary fp32 inputs, from the fp64 stage values ``st`` of
+    tests/_prop_probe.model(..., dt=float64) for one ray.  Returns per-entry bounds for
+    ``pdf``, ``cdf`` (at the knots), ``ci`` (at the proposal edges), ``ws``, ``G``, ``grad`` and ``loss``:
+
+    * inputs: cdf_j = fl(1 - trans_j) (u |cdf_j|; cdf_n = 1 exactly), knots fl(s -+ r) (u |knot|);
+    * w_n = fl(fl(dc) / fl(ds)): (e_c_j + e_c_j+1) / ds + 3 u |w_n|; events fl(fl(w_r - w_l) / 2 r): (e_wr + e_wl) / 2 r + 2 u |y|;
+    * slope_t = sum of t + 1 events: t u sum |ev|, + what the events themselves carry: the two events +y_j (at knot s_j - r)
+      and -y_j (at s_j + r) hold the same rounded y_j, so only the edges j_b .. j_a straddling segment t count, and their sum
+      telescopes to (w_r[j_a] - w_l[j_b]) / 2 r: (e_wr[j_a] + e_wl[j_b]) / 2 r + sum over j_b .. j_a of 2 u |y_j|;
+    * pdf term dx slope: e_dx |slope| + |dx| e_slope + u |term| with e_dx = e_knot_t + e_knot_t+1 + u |dx|; pdf at knot t + 1:
+      sum of the term errors + t u sum |terms| (max(., 0) is 1-Lipschitz);
+    * area 0.5 (p_t + p_t+1) dx: 0.5 (e_p_t + e_p_t+1 + u |p_t + p_t+1|) |dx| + 0.5 |p_t + p_t+1| e_dx + u |area|; cdf: sum + t u sum |area|;
+    * CI = cdf_i0 + num (p0 + p1 off + p0 (1 - off)) / 2: e_num = e_knot_i0 + u |num|, e_off = min(1, (e_num + off e_den) / den
+      + u off) (off is clipped to [0, 1]; a bracket that differs between the precisions only when q is within e_knot of a knot
+      changes the value to second order: the interpolant is continuous with a continuous derivative), inner: (2 - off) e_p0
+      + off e_p1 + |p1 - p0| e_off + 4 u (2 |p0| + |p1|), product and sum one rounding each;
+    * w_s = fl(CI_j+1 - CI_j): the area errors of the common prefix cancel, what remains is the sum of e_area between the two
+      brackets, both prefixes' additions, both interpolations; w_p = fl(c_j+1 - c_j), d = max(fl(w_s - w_p), 0): e_d = e_ws + u |w_p| + u |w_s - w_p|;
+    * |dG| <= (2 / den + 2 d / den^2) e_d + c_prop_G(False) u |G| (G is continuous across the hinge: the bound holds on
+      both sides), a term: (2 d / den) e_d + c_prop_term(False) u term;
+    * grad_j: (e_G_j-1 + e_G_j + 2 u (|G_j-1| + |G_j|)) scale;  loss: sum of the term errors + (m + 1) u sum of terms, times scale."""
+    a = lambda x: np.abs(np.asarray(x, np.float64))   # noqa: E731
+    c, xr, ev = st["c"], st["xr"], st["ev"]
+    K = xr.size
+    e_c = U * a(c)
+    e_c[-1] = 0.0
+    # w_n and the events, in the order of the final edges
+    dsf = np.diff(st["s"])
+    e_wn = (e_c[1:] + e_c[:-1]) / dsf + 3 * U * a(st["wn"])
+    e_wr, e_wl = np.append(e_wn, 0.0), np.insert(e_wn, 0, 0.0)
+    # the events in knot order: position of A_j / B_j among the knots (the model's own ranks)
+    e_x = U * a(xr)
+    t = np.arange(K - 1, dtype=np.float64)
+    # slope of segment t = sum of the events of the edges j_b .. j_a whose knots straddle it = (w_r[j_a] - w_l[j_b]) / 2 r: the
+    # errors the weights carry telescope to the two outermost ones; each y_j in between adds its own two roundings
+    seg = np.arange(K - 1)
+    ja, jb = np.searchsorted(st["pa"], seg, "right") - 1, np.searchsorted(st["pb"], seg, "right")
+    is_open = jb <= ja
+    e_in = np.where(is_open, e_wr[np.maximum(ja, 0)] + e_wl[np.minimum(jb, e_wl.size - 1)], 0.0) / (2 * st["pulse"])
+    y_cum = np.insert(_prefix(2 * U * a(st["y"])), 0, 0.0)
+    e_own = np.where(is_open, y_cum[np.maximum(ja, 0) + 1] - y_cum[np.minimum(jb, e_wl.size - 1)], 0.0)
+    e_slope = e_in + e_own + t * U * _prefix(a(ev[:K - 1]))
+    dx, slope = a(st["dx"]), a(st["slope"])
+    e_dx = e_x[1:] + e_x[:-1] + U * dx
+    e_v = e_dx * slope + dx * e_slope + U * a(st["v"])
+    e_pdf = np.insert(_prefix(e_v) + t * U * _prefix(a(st["v"])), 0, 0.0)
+    psum = a(st["psum"])
+    e_area = 0.5 * (e_pdf[1:] + e_pdf[:-1] + U * psum) * dx + 0.5 * psum * e_dx + U * a(st["area"])
+    e_cdf_in, e_cdf_add = np.insert(_prefix(e_area), 0, 0.0), np.insert(t * U * _prefix(a(st["area"])), 0, 0.0)
+    e_cdf = e_cdf_in + e_cdf_add
+    i0, i1 = st["i0"], st["i1"]
+    num, den, off = a(st["num"]), a(st["den"]), a(st["off"])
+    p0, p1 = a(st["pdf"][i0]), a(st["pdf"][i1])
+    e_num = e_x[i0] + U * num
+    e_den = e_x[i0] + e_x[i1] + U * den
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e_off = np.where(den > 0, np.minimum(1.0, (e_num + off * e_den) / den + U * off), 0.0)
+    e_inner = (2.0 - off) * e_pdf[i0] + off * e_pdf[i1] + a(st["pdf"][i1] - st["pdf"][i0]) * e_off + 4 * U * (2 * p0 + p1)
+    e_prod = e_num * a(st["inner"]) + num * e_inner + U * a(st["prod"])
+    e_ci = e_cdf[i0] + 0.5 * e_prod + U * a(st["ci"])
+    # w_s = CI_j+1 - CI_j: the area errors the two prefixes share cancel (the additions' own roundings do not)
+    e_loc = e_cdf_add[i0] + 0.5 * e_prod + U * a(st["ci"])
+    e_ws = a(e_cdf_in[i0][1:] - e_cdf_in[i0][:-1]) + e_loc[1:] + e_loc[:-1] + U * a(st["ws"])
+    d, dn = st["d"], st["dn"]
+    e_d = e_ws + U * a(st["wp"]) + U * a(st["ws"] - st["wp"])
+    e_G = (2.0 / dn + 2.0 * d / dn ** 2) * e_d + c_prop_G(False) * U * a(st["G"])
+    e_term = (2.0 * d / dn) * e_d + c_prop_term(False) * U * st["term"]
+    gm, gj = np.insert(a(st["G"]), 0, 0.0), np.append(a(st["G"]), 0.0)
+    e_grad = (np.insert(e_G, 0, 0.0) + np.append(e_G, 0.0) + 2 * U * (gm + gj)) * abs(scale)
+    m = d.size
+    e_loss = (e_term.sum() + (m + 1) * U * st["term"].sum()) * abs(scale)
+    return dict(pdf=e_pdf, cdf=e_cdf, ci=e_ci, ws=e_ws, G=e_G, grad=e_grad, loss=e_loss)
+
+
+def assert_prop_bound(got, ref, err, what: str, report: dict = None) -> float:
+    """|got - ref| <= err entry by entry (numpy arrays; err = 0 -> exactly equal); prints and returns the worst err / bound."""
+    return assert_bound(np.asarray(got, np.float64), np.asarray(ref, np.float64), np.asarray(err, np.float64) / U, 1.0, what, report=report)
+
+
+def prop_pdf_bound(st: dict, scale: float) -> dict:
+    """First-order bounds for mode 1 (_pdf_loss) on arbitrary fp32 inputs, from the fp64 stage values of
+    tests/_prop_probe.model_pdf(..., dt=float64) for one ray: cdf_j = fl(1 - trans_j) (u |cdf_j|), w = fl(dc)
+    (e_w = e_c_j + e_c_j+1 + u |w|), w_outer one rounding, d = max(fl(w - w_outer), 0): e_d = e_w + u |w_outer| + u |w - w_outer|;
+    den = fl(w + eps): e_den = e_w + C_PROP_DEN u den; g = -2 d / den: (2 / den) e_d + (2 d / den^2) e_den + 2 u |g| (g is
+    continuous across the hinge); an entry sums the g of the final intervals whose brackets end there -- every interval
+    whose hinge is active or within e_d of it counts as a hit --: sum e_g + hits u sum |g|, + u for the product with scale.
+    A term d^2 / den: (2 d / den) e_d + (d^2 / den^2) e_den + 3 u term; the loss over n terms: + (n + 1) u sum."""
+    a = lambda x: np.abs(np.asarray(x, np.float64))   # noqa: E731
+    c, w, wo, d, dn, g = st["c"], st["w"], st["wo"], st["d"], st["dn"], st["g"]
+    e_c = U * a(c)
+    e_c[-1] = 0.0
+    e_w = e_c[1:] + e_c[:-1] + U * a(w)
+    e_d = e_w + U * a(wo) + U * a(w - wo)
+    e_den = e_w + C_PROP_DEN * U * dn
+    e_g = (2.0 / dn) * e_d + (2.0 * d / dn ** 2) * e_den + 2 * U * a(g)
+    pot = (w - wo) > -e_d
+    m1 = st["G"].size
+    e_sum, hits, gabs = np.zeros(m1), np.zeros(m1), np.zeros(m1)
+    for idx in (st["ir"], st["il"]):
+        np.add.at(e_sum, idx[pot], e_g[pot])
+        np.add.at(hits, idx[pot], 1.0)
+        np.add.at(gabs, idx[pot], a(g)[pot])
+    e_grad = (e_sum + (hits + 1.0) * U * gabs) * abs(scale)
+    e_term = (2.0 * d / dn) * e_d + (d * d / dn ** 2) * e_den + 3 * U * st["term"]
+    e_loss = (e_term.sum() + (d.size + 1) * U * st["term"].sum()) * abs(scale)
+    return dict(grad=e_grad, loss=e_loss)

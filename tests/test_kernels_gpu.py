@@ -561,6 +561,10 @@ def test_prop_loss_matches_oracle(hip_lib, oracle, R, n, m, level):
     # individual entries sit on hinges (max(w_s - w_p, 0)): allow a handful of entries whose hinge flips on rounding
     bad = err > 2e-4 * scale + 2e-3 * want_grad.abs()
     assert int(bad.sum()) <= max(2, got.numel() // 20000), f"{int(bad.sum())} gradient entries off; max err {float(err.max()):.3e} vs scale {scale:.3e}"
+    if R <= 64:  # beside the asserts above, at the small shapes (the fp64 mask form is not run at R = 8192): every entry, no exceptions
+        from tests._prop_probe import check_total_and_gradient
+        check_total_and_gradient(s_fin, trans, s_p, c_p, pulses[level], True, scaler / (R * m), 0.5, float(loss), got.numpy(),
+                                 f"prop_loss R={R} n={n} m={m} level {level}")
 
 
 @pytest.mark.parametrize("R,n,m", [(513, 128, 64), (7, 32, 48)])
@@ -585,6 +589,9 @@ def test_pdf_loss_matches_torch_form(hip_lib, R, n, m):
     assert abs(float(got) - float(want)) <= 1e-4 * abs(float(want)) + 1e-12
     sc = float(cp.grad.abs().max())
     assert float((cd.grad.cpu() - cp.grad).abs().max()) <= 2e-4 * sc + 1e-12
+    if R <= 64:  # beside the asserts above: the per-entry fp64 bound (hit counts and abs-sums of the LDS atomics)
+        from tests._prop_probe import check_total_and_gradient
+        check_total_and_gradient(s_fin, trans, s_p, c_p, 0.0, False, 7.0 / (R * n), 1.0, float(got), cd.grad.cpu().numpy(), f"pdf_loss R={R} n={n} m={m}")
 
 
 # ----------------------------------------------------------------------------- per-ray epilogue and pixel losses

@@ -9,6 +9,13 @@
 // exclusive cumsum of sigma*dt (and the reverse-mode suffix sums) are wave scans built from DPP
 // shuffles -- no LDS traffic, no atomics, fully coalesced (R,S) loads/stores.  S is unbounded
 // (chunks of 64 with a carried prefix); at the metric shape S=128 a ray is exactly two chunks.
+//
+// Tests: tests/test_composite_exact_gpu.py holds every kernel of this file entry by entry -- to the fp64 restatement
+// exactly on probes whose fp32 operations are all exact (tests/_composite_probe.py: walls with sigma*dt in {0, 128},
+// dyadic accumulate / blend inputs), and inside a derived first-order bound on realistic rays (tests/_bounds.py:
+// render_bounds, dsigma_bound, epilogue_bounds, blend_c).  tests/_composite_model.py is a numpy model of the chunking,
+// carries, tail masking, median latch, four-wave split and quads below; tests/test_composite_bounds_cpu.py runs it and its
+// mutants against the same probes.  A change to the summation structure here needs the same change in that model.
 #include "common.h"
 
 namespace emer {

@@ -419,3 +419,169 @@ def prop_pdf_bound(st: dict, scale: float) -> dict:
     e_term = (2.0 * d / dn) * e_d + (d * d / dn ** 2) * e_den + 3 * U * st["term"]
     e_loss = (e_term.sum() + (d.size + 1) * U * st["term"].sum()) * abs(scale)
     return dict(grad=e_grad, loss=e_loss)
+
+
+# ------------------------------------------------------------------------------------------- compositing kernels
+# csrc/composite.hip and the ray epilogue of csrc/rayloss.hip on arbitrary fp32 inputs (tests/_composite_probe.py has the
+# fp64 restatement whose values and abs-sums these take).  First order, one rounding (relative u) per fp32 operation; a
+# contracted multiply-add only removes roundings.  A sum of terms through any tree puts each term through at most
+# `depth` additions, each seeing a partial sum that is at most the abs-sum: depth u abs_sum.
+#
+# The one constant that is not derived is the device expf's error.  Measured on an MI355X through render_weights_fwd itself
+# (S = 2, dt = 1, sigma_1 = 0: trans[:, 1] = expf(-sigma_0)), 11.5 million arguments in [0, 100] (a uniform grid, uniform
+# random, dense in [0, 2], log-spaced down to e^-30, every multiple of 0.25) against float64 exp of the fp32 argument:
+# at most 0.836 ulp (at x = 62.4916; 6.3 % of the results are not the correctly rounded one), results below the normal range
+# are kept and within one subnormal step.  E_EXPF is that maximum rounded up to the next integer plus one ulp of margin;
+# one ulp is at most 2 u relative.  tests/test_composite_exact_gpu.py::test_device_expf_error_is_inside_E_EXPF repeats a
+# smaller sweep and fails if the device's expf ever leaves E_EXPF - 1.
+E_EXPF_MEASURED = 0.836  # ulps
+E_EXPF = 2.0
+TINY = 2.0 ** -126       # absolute floor: results below the normal range (kept or flushed)
+
+
+def _chunk(S):
+    return np.arange(S) // 64
+
+
+def render_bounds(rf: dict) -> dict:
+    """render_weights_fwd / composite_rgb_fwd from ``ref_render``'s values (x = sigma dt, A = inclusive cumsum |x|):
+
+    * x = fl(sigma fl(te - ts)): 2 u |x|;
+    * excl_i: every x_j passes the 6 steps of the wave scan, `incl - sdt`, `carry +` and one carry accumulation per earlier
+      chunk c_i: depth 8 + c_i, partial sums at most A_i; what the x_j carry themselves: 2 u A_i  ->  (10 + c_i) u A_i;
+    * T = expf(-excl): the ABSOLUTE error of excl becomes a RELATIVE error of T: expm1(e_excl) + 2 E_EXPF u;
+    * e = expf(-x): (expm1(e_x) + 2 E_EXPF u) e; alpha = fl(1 - e): e_e + u alpha -- absolute, u-sized even where alpha is tiny;
+    * w = fl(T alpha): T e_alpha + alpha e_T + u w;  cdfs = fl(1 - T): e_T + u |1 - T| (the last column is written as 1);
+    * sum w, sum w mid: each lane adds one w per chunk, then the 6 steps of the wave sum: depth n_chunks + 6; mid = fl(fl(a + b) / 2)
+      and the product: 2 u w mid;
+    * the median's inclusive cumsum of w: 6 scan steps, `wcarry +`, one carry per earlier chunk: (7 + c_i) u cumsum(w) + cumsum(e_w).
+    """
+    x, A, T, e, al, w, mid = (rf[k] for k in ("x", "A", "T", "e", "al", "w", "mid"))
+    S = x.shape[1]
+    c = _chunk(S)[None, :]
+    nch = -(-S // 64)
+    e_x = 2 * U * np.abs(x)
+    e_excl = (10 + c) * U * A
+    rel = 2 * E_EXPF * U
+    r_T = np.expm1(e_excl)
+    e_T = T * (r_T + rel * (1 + r_T)) + TINY
+    r_e = np.expm1(e_x)
+    e_e = e * (r_e + rel * (1 + r_e)) + TINY
+    e_al = e_e + U * np.abs(al)
+    e_w = T * e_al + al * e_T + e_T * e_al + U * w + TINY
+    e_cdf = np.concatenate([e_T + U * np.abs(1 - T), np.zeros((x.shape[0], 1))], 1)
+    e_sum = e_w.sum(1) + (nch + 6) * U * w.sum(1)
+    e_mid = (e_w * mid + 2 * U * w * mid).sum(1) + (nch + 6) * U * (w * mid).sum(1)
+    e_cw = np.cumsum(e_w, 1) + (7 + c) * U * np.cumsum(w, 1)
+    return dict(x=e_x, T=e_T, e=e_e, al=e_al, w=e_w, cdfs=e_cdf, wsum=e_sum, wmid=e_mid, cw=e_cw,
+                weights=e_w, trans=e_T, alphas=e_al)
+
+
+def median_ambiguous(rf: dict, rb: dict) -> np.ndarray:
+    """Rays whose fp64 inclusive cumsum of w comes within its bound of 0.5 at some sample: the median may slip there."""
+    return (np.abs(rf["cw"] - 0.5) <= rb["cw"]).any(1)
+
+
+def dsigma_bound(rf: dict, rb: dict, g: dict) -> np.ndarray:
+    """d_sigma_i = fl(dt (gw T e - later + gA e)) of render_weights_bwd / composite_rgb_bwd.  ``g`` (``ref_render_bwd`` plus
+    gw_abs, gT_abs and the per-ray errors e_g0, e_g1 that reach gw):
+
+    * gw = dW [+ sum_c g_c rgb_c] + (g0 + g1 mid): at most 6 roundings on the abs-sum gw_abs, plus e_g0 + e_g1 mid;
+    * P = gw T e: e_gw T e + |gw| (e_T e + T e_e) + 2 u |P|;
+    * term_k = gw_k w_k + gT_k T_k: e_gw w + |gw| e_w + |gT| e_T + 4 u (|gw| w + gT_abs T) (two products, one sum, and the
+      wrapper's fp32 sum dT - dC);
+    * later_i = suffix + (sfx_incl - term): 6 scan steps, the subtraction, `suffix +`, one carry per later chunk: depth
+      8 + (n_chunks - 1 - c_i) on the INCLUSIVE abs-sum of the terms from i on -- `sfx_incl - term` cancels, so it is held to
+      the abs-sum, never to the result;
+    * Q = gA e: |gA| e_e + u |Q|;
+    * `P - later + Q` and the product with dt = fl(te - ts): 4 u on |P| + abs-sum + |Q|, again not on the result."""
+    T, e, w, mid, dts = (rf[k] for k in ("T", "e", "w", "mid", "dts"))
+    S = T.shape[1]
+    c = _chunk(S)[None, :]
+    nch = -(-S // 64)
+    a = np.abs
+    gw, gT, gA = g["gw"], g["gT"], g["gA"]
+    e_gw = 6 * U * g["gw_abs"] + g["e_g0"][:, None] + g["e_g1"][:, None] * mid
+    e_P = e_gw * T * e + a(gw) * (rb["T"] * e + T * rb["e"] + rb["T"] * rb["e"]) + 2 * U * a(g["P"])
+    t_abs = (a(gw) + e_gw) * w + g["gT_abs"] * T
+    e_term = e_gw * (w + rb["w"]) + a(gw) * rb["w"] + a(gT) * rb["T"] + 4 * U * t_abs
+    rc = lambda v: np.cumsum(v[:, ::-1], 1)[:, ::-1]   # noqa: E731
+    L_abs = rc(t_abs)
+    e_L = np.concatenate([rc(e_term)[:, 1:], np.zeros_like(T[:, :1])], 1) + (8 + nch - 1 - c) * U * L_abs
+    e_Q = a(gA) * rb["e"] + U * a(g["Q"])
+    return a(dts) * (e_P + e_L + e_Q + 4 * U * (a(g["P"]) + L_abs + a(g["Q"])))
+
+
+C_EPI_GO = 8.0   # go = do - gd y / (o o) - sum_c g_c sky_c: a term's own roundings (<= 3) + 4 subtractions, slack 1
+
+
+def epilogue_bounds(ep: dict, e_sum=None, e_mid=None, e_acc=None) -> dict:
+    """ray_epilogue_fwd/bwd and the per-ray part of composite_rgb from ``ref_epilogue``'s values.  e_sum / e_mid / e_acc: the
+    errors the inputs (sum w, sum w mid, accumulated colour) already carry -- 0 when the kernel is given them exactly.
+
+    * opacity = clamp(sum w): exact given its input; e_o = e_sum where the clamp passes (or may pass), else 0;
+    * depth = fl(y / o): e_mid / o + |y| e_o / o^2 + u |depth|;
+    * rgb = fl(acc + fl(sky fl(1 - o))): e_acc + |sky| e_o + 2 u |sky (1 - o)| + u (|acc| + |sky (1 - o)|);
+    * g1 = fl(gd / o): |gd| e_o / o^2 + u |g1|;  d_sky = fl(g fl(1 - o)): |g| e_o + 2 u |g (1 - o)|;
+    * g0: C_EPI_GO u on the abs-sum of go, plus |gd| (e_mid / o^2 + 2 |y| e_o / o^3), on the rays of ``ep["passes"]``; exactly
+      0 on the others.  The caller evaluates the reference with the clamp branch the kernel took
+      (tests/_composite_probe.clamp_branch), so a ray whose sum w sits on a clamp bound gets no allowance."""
+    a = np.abs
+    o, st = ep["opacity"], ep["stats"]
+    R = o.shape[0]
+    z = np.zeros(R)
+    e_sum, e_mid = (z if e_sum is None else e_sum), (z if e_mid is None else e_mid)
+    lo = float(np.float32(1e-6))
+    inside = (st[:, 0] >= lo - e_sum) & (st[:, 0] <= 1.0 + e_sum)
+    e_o = np.where(inside, e_sum, 0.0)
+    y = st[:, 1]
+    out = dict(opacity=e_o, depth=e_mid / o + a(y) * e_o / o ** 2 + U * a(ep["depth"]))
+    if "rgb" in ep:
+        e_acc = np.zeros_like(ep["rgb"]) if e_acc is None else e_acc
+        sk = ep["rgb"] - ep["acc"]           # sky (1 - o), or 0 without a sky
+        sky_abs = np.zeros_like(sk) if ep.get("sky") is None else a(ep["sky"])
+        out["rgb"] = e_acc + sky_abs * e_o[:, None] + 2 * U * a(sk) + U * (a(ep["acc"]) + a(sk))
+    if "d_sky" in ep:
+        out["d_sky"] = ep["g_abs"] * e_o[:, None] + 2 * U * a(ep["d_sky"])
+    dd = ep["dd"]
+    out["g1"] = a(dd) * e_o / o ** 2 + U * a(ep["g1"])
+    e_go = C_EPI_GO * U * ep["go_abs"] + a(dd) * (e_mid / o ** 2 + 2 * a(y) * e_o / o ** 3)
+    out["g0"] = np.where(ep["passes"], e_go, 0.0)
+    return out
+
+
+def c_accumulate(S: int, C) -> float:
+    """out[r, c] = sum_s w v against sum |w v|: small kernel (C <= 8 or no values): the product, ceil(S / 64) additions per
+    lane, 6 wave-sum steps; wide kernel: the product and S sequential additions.  Slack 1."""
+    return float(-(-S // 64) + 8) if (C is None or C <= 8) else float(S + 2)
+
+
+def c_accumulate_dw(C) -> float:
+    """d_w = sum_c go v against sum |go v|: small: C products, C - 1 additions; wide: product, ceil(C / 64) additions per
+    lane, 6 wave-sum steps.  Slack 1.  (No values: d_w is go itself, exactly.)"""
+    return float(C + 1) if C <= 8 else float(-(-C // 64) + 8)
+
+
+def blend_c(S: int, wide_C=None) -> dict:
+    """Rounding counts of blend_accumulate (wide_C None) and blend_accumulate_wide against the abs-sums of
+    ``ref_blend`` / ``ref_blend_wide``; slack 1 in each.  inv = fl(1 / fl(sigma + 1e-6f)): 2; a = sigma_s inv: 3;
+    ka = a fl(1 - shadow): 5.
+
+    narrow: a forward term w (ka rgb_s + b rgb_d): 8, the lane's chain ceil(S / 64), the wave sum 6; sum w shadow^2: 2 + chain;
+      <g, rgb>: 3; d_w = ka gS + b gD + gs sh sh: 11; d_rgb_s = g (w ka): 7; d_rgb_d = g (w b): 5; d_shadow = w (2 gs sh - a gS): 9;
+      d_sigma_s = (w (1 - sh) gS) inv: 9; d_sigma_d = (w gD) inv: 7; d_sigma = -(da sigma_s + db sigma_d) inv inv: 14.
+    wide: a forward term w (a f_s + b f_d): 6, a chain of ceil(S / 8) + 1 per wave, a0 + a1 and two cross-wave additions: 3;
+      m = <g, f>: cm = the product, ceil(C / 64) per lane, 6 wave-sum steps; d_w = a mS + b mD: cm + 5; d_f = g (w sigma inv): 5;
+      d_sigma_s = (w mS) inv: cm + 4; d_sigma = ...: cm + 9."""
+    if wide_C is None:
+        ch = -(-S // 64)
+        return dict(acc=15.0 + ch, acs=9.0 + ch, d_w=12.0, d_rs=8.0, d_rd=6.0, d_sh=10.0, d_ss=10.0, d_sd=8.0, d_sig=15.0)
+    cm = -(-wide_C // 64) + 7
+    return dict(acc=float(-(-S // 8) + 11), d_w=cm + 6.0, d_fs=6.0, d_fd=6.0, d_ss=cm + 5.0, d_sd=cm + 5.0, d_sig=cm + 10.0)
+
+
+def assert_err_bound(got, ref, err, what: str, report: dict = None) -> float:
+    """|got - ref| <= err entry by entry (numpy; err = 0 -> exactly equal); prints and returns the worst err / bound."""
+    ref = np.asarray(ref, np.float64)
+    return assert_bound(np.asarray(got, np.float64).reshape(ref.shape), ref, np.broadcast_to(np.asarray(err, np.float64), ref.shape) / U, 1.0,
+                        what, report=report)

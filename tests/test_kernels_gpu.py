@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _composite_probe as CP
 from tests._bounds import assert_bound, c_atomic, c_forward, c_input_grad, c_sliced
 
 pytestmark = pytest.mark.gpu
@@ -352,6 +353,13 @@ def test_render_weights(hip_lib, oracle, R, S):
     ((w2 * gw).sum() + (T2 * gT).sum() + (c2 * gc).sum() + (st2 * gs).sum() + (a2 * ga).sum()).backward()
     ref_g = s64.grad.numpy()
     np.testing.assert_allclose(sgd.grad.cpu().numpy(), ref_g, rtol=1e-4, atol=1e-5 * np.abs(ref_g).max())
+    # every entry inside its first-order fp64 bound (tests/_bounds.py render_bounds, dsigma_bound); the median exact except on
+    # a ray whose cumsum of w comes within its bound of 0.5
+    n = lambda t: t.detach().cpu().numpy()   # noqa: E731
+    p = dict(ts=ts.numpy(), te=te.numpy(), sg=sg.numpy(), dW=gw.numpy(), dT=gT.numpy(), dA=ga.numpy(), dC=gc.numpy(),
+             dS=torch.cat([gs, torch.zeros(R, 2)], -1).numpy())
+    CP.check_real_render(p, dict(weights=n(w), trans=n(T), alphas=n(a), cdfs=n(cdfs), stats=n(stats), d_sigma=n(sgd.grad)),
+                         f"render_weights R={R} S={S}", allow_ambiguous=True)
 
 
 @pytest.mark.parametrize("C", [None, 1, 3, 6, 64, 100])
@@ -374,6 +382,8 @@ def test_accumulate(hip_lib, oracle, C):
     else:
         np.testing.assert_allclose(wd.grad.cpu().numpy(), torch.einsum("rc,rsc->rs", go, v).numpy(), rtol=1e-4, atol=1e-5)
         np.testing.assert_allclose(vd.grad.cpu().numpy(), (w[..., None] * go[:, None, :]).numpy(), rtol=1e-6, atol=1e-7)
+    CP.check_real_accumulate(dict(w=w.numpy(), v=None if v is None else v.numpy(), go=go.numpy()), out.detach().cpu().numpy(),
+                             wd.grad.cpu().numpy(), None if v is None else vd.grad.cpu().numpy(), f"accumulate C={C}")
 
 
 @pytest.mark.parametrize("unbounded", [True, False])
@@ -996,6 +1006,13 @@ def test_blend_accumulate_matches_torch(hip_lib, R, S, with_shadow):
     for k in names:
         ref_g = d64[k].grad
         np.testing.assert_allclose(dv[k].grad.cpu().numpy(), ref_g.numpy(), rtol=1e-4, atol=2e-6 * float(ref_g.abs().max()), err_msg=k)
+    # per entry (tests/_bounds.py blend_c); sigma_s and sigma_d also carry the gradient of the device sum sigma
+    if R <= 257:
+        p = dict(w=w.numpy(), sig=sig.detach().cpu().numpy(), ss=ss.numpy(), sd=sd.numpy(), rs=rs.numpy(), rd=rd.numpy(),
+                 sh=sh.numpy()[..., 0] if with_shadow else None, g_rgb=g_rgb.numpy(), g_sh=g_sh.numpy() if with_shadow else None)
+        got = {"d_" + k: dv[k].grad.cpu().numpy().reshape(cpu[k].shape[:3] if cpu[k].shape[-1] == 3 else (R, S)) for k in names}
+        got.update(acc=acc.detach().cpu().numpy(), acs=acs.detach().cpu().numpy()[:, 0] if with_shadow else None)
+        CP.check_real_blend_through_sum(p, got, f"blend R={R} S={S}")
 
 
 def test_nonfinite_gradient_is_reported_before_the_scatter(hip_lib, oracle, monkeypatch):
@@ -1184,6 +1201,16 @@ def test_composite_rgb_equals_the_three_kernel_rendering(hip_lib, R, S, with_rgb
     for a, b in zip(res[False][1], res[True][1]):
         scale = a.abs().max().item() + 1e-30
         assert (a - b).abs().max().item() <= 2e-6 * scale, f"gradient differs: {(a - b).abs().max().item():.3e} of {scale:.3e}"
+    # the fused kernel against the fp64 restatement itself, entry by entry (a slip shared with the three kernels shows here)
+    if R <= 513:
+        n = lambda t: t.detach().cpu().numpy()   # noqa: E731
+        p = dict(ts=n(t0), te=n(t1), sg=sig.numpy(), rgb=rgb.numpy() if with_rgb else None, sky=sky.numpy() if (with_rgb and with_sky) else None,
+                 dW=n(ups["w"]), dT=n(ups["T"]), d_opa=n(ups["opa"]), d_dep=n(ups["dep"]), d_out=n(ups["rgb"]) if with_rgb else None)
+        outs, grads = res[True]
+        got = dict(weights=n(outs[0]), trans=n(outs[1]), t_mid=n(outs[2]), t_dist=n(outs[3]), opacity=n(outs[4])[:, 0], depth=n(outs[5])[:, 0],
+                   median=n(outs[6])[:, 0], rgb_out=n(outs[7]) if with_rgb else None, d_sigma=n(grads[0]),
+                   d_rgb=n(grads[1]) if with_rgb else None, d_sky=n(grads[2]) if (with_rgb and with_sky) else None)
+        CP.check_real_composite(p, got, f"composite_rgb R={R} S={S}", allow_ambiguous=True, wsum=n(stats)[:, 0])
 
 
 @pytest.mark.parametrize("R,S,C", [(257, 128, 64), (33, 50, 100), (2048, 128, 64)])
@@ -1214,5 +1241,11 @@ def test_blend_accumulate_wide_matches_the_reference_expression(hip_lib, R, S, C
         scale = float(b.grad.abs().max()) + 1e-30
         err = float((a.grad.cpu().double() - b.grad).abs().max())
         assert err <= 5e-6 * scale, f"d {name}: {err:.3e} of {scale:.3e}"
+    if R <= 257:   # per entry (tests/_bounds.py blend_c)
+        n = lambda t: t.detach().cpu().numpy()   # noqa: E731
+        p = dict(w=w.numpy(), sig=n(sg)[..., 0], ss=ss.numpy()[..., 0], sd=sd.numpy()[..., 0], fs=fs.numpy(), fd=fd.numpy(), g_acc=up.numpy())
+        got = dict(acc=n(acc), d_w=n(leaves[0].grad), d_ss=n(leaves[1].grad)[..., 0], d_sd=n(leaves[2].grad)[..., 0], d_fs=n(leaves[3].grad),
+                   d_fd=n(leaves[4].grad), d_sig=n(sg.grad)[..., 0])
+        CP.check_real_blend_through_sum(p, got, f"blend wide R={R} S={S} C={C}", wide=True)
 
 

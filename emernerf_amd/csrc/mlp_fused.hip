@@ -616,6 +616,57 @@ __device__ __forceinline__ void dw_blocks(f32x16 (&acc)[NQ], const SwP &a, const
 #undef EMER_DWB
 }
 
+// ---- small pieces that the kernels with register-resident weight gradients share (neck_bwdw, rgb_bwdw16 / rgb_bwdwr, rmlp_bwdw) --------
+// A gradient lives as 32 x 32 blocks acc[P][Q]: lane (j, h), register r = dW[32 P + 8 (r >> 2) + 4 h + (r & 3)][32 Q + j].
+template <int NP, int NQ>
+__device__ __forceinline__ void zero_blocks(f32x16 (&acc)[NP][NQ]) {
+#pragma unroll
+    for (int P = 0; P < NP; ++P)
+#pragma unroll
+        for (int Q = 0; Q < NQ; ++Q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[P][Q][r] = 0.0f;
+}
+// Wave w's turn of the cross-wave sum through LDS into dst [32 NP][PITCH]: wave 0 stores, the others add (the caller serialises the waves
+// with barriers).  The one-wave rgb kernels share it.  neck_bwdw_kernel and rmlp_bwdw_kernel keep this loop nest written out: called from
+// there (tried with the column limit of their odd last block as a parameter) the wave loop around it gets unrolled, the code grows by up
+// to 44 % and the register allocation of the whole kernel moves (neck <4, 4, 1>: scratch 140 -> 144 bytes per lane) -- for an epilogue.
+template <int PITCH, int NP, int NQ>
+__device__ __forceinline__ void fold_blocks(float *dst, int w, const f32x16 (&acc)[NP][NQ], int lane) {
+    const int j32 = lane & 31, h32 = lane >> 5;
+#pragma unroll
+    for (int P = 0; P < NP; ++P)
+#pragma unroll
+        for (int Q = 0; Q < NQ; ++Q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float *q = dst + (32 * P + 8 * (r >> 2) + 4 * h32 + (r & 3)) * PITCH + 32 * Q + j32;
+                *q = (w == 0) ? acc[P][Q][r] : *q + acc[P][Q][r];
+            }
+}
+// Column sums as to_rows() leaves them (s[p]: this lane's four rows of feature 16 p + m) -> every lane holds the sum over the tile's rows
+template <int N>
+__device__ __forceinline__ void finish_colsums(float (&s)[N]) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) { s[p] += __shfl_xor(s[p], 16, 64); s[p] += __shfl_xor(s[p], 32, 64); }
+}
+// ... and wave w's turn of their cross-wave sum into the bias row of the reduction buffer (lanes with g == 0 only)
+template <int N>
+__device__ __forceinline__ void fold_bias(float *row, int w, const float (&s)[N], int m) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) row[16 * p + m] = (w == 0) ? s[p] : row[16 * p + m] + s[p];
+}
+// The input tile as the operand of dW0 is needed at the end of the tile body: parked in LDS ([KT0][3][64] u32x2, `park` = this lane's
+// entry), not in 6 KT0 registers
+template <int KT0>
+__device__ __forceinline__ void park_rows(u32x2 *park, const Opd<(KT0 + 1) / 2> &xo, const SelE sel) {
+#pragma unroll
+    for (int b = 0; b < KT0; ++b) {
+        const SwT t = to_rows<(KT0 + 1) / 2>(xo, b, sel);
+        park[(3 * b + 0) * 64] = t.h; park[(3 * b + 1) * 64] = t.m; park[(3 * b + 2) * 64] = t.l;
+    }
+}
+
 constexpr int neckw_threads(int kt0, int no = 1) { return no == 2 ? 256 : 512; }
 // (512 threads = 8 waves, ONE workgroup per CU = 2 waves per SIMD, <= 256 registers; the weights, 48-72 KB, are staged once per CU and
 // leave room for 7-10 KB of per-wave staging)
@@ -656,18 +707,8 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
     constexpr int QB = (KT0 + 1) / 2;   // 32-feature blocks of the encoding (the last one half empty when KT0 is odd)
     f32x16 bw1[2 * NO][2], bw0[2][QB];
     float ab1[4 * NO], ab0[4];      // bias gradients: this lane's rows 4 g .. 4 g + 3 of feature 16 p + m
-#pragma unroll
-    for (int P = 0; P < 2 * NO; ++P)
-#pragma unroll
-        for (int Q = 0; Q < 2; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bw1[P][Q][r] = 0.0f;
-#pragma unroll
-    for (int P = 0; P < 2; ++P)
-#pragma unroll
-        for (int Q = 0; Q < QB; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bw0[P][Q][r] = 0.0f;
+    zero_blocks(bw1);
+    zero_blocks(bw0);
 #pragma unroll
     for (int p = 0; p < 4 * NO; ++p) ab1[p] = 0.0f;
 #pragma unroll
@@ -749,11 +790,7 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
                 f32x4 h[4];
                 init_bias<4>(b0l, g, h);
                 tgemm<KS0, 4, false>(w0fp, xo, h);
-#pragma unroll
-                for (int b = 0; b < KT0; ++b) {   // operand of dW0, needed at the end of the tile: parked in LDS, not in 6 KT0 registers
-                    const SwT t = to_rows<KS0>(xo, b, sel);
-                    park[(3 * b + 0) * 64] = t.h; park[(3 * b + 1) * 64] = t.m; park[(3 * b + 2) * 64] = t.l;
-                }
+                park_rows<KT0>(park, xo, sel);   // operand of dW0
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -820,10 +857,8 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
     __syncthreads();
     float *red = reinterpret_cast<float *>(smem);   // dW1 [64 NO][64] | db1 [64 NO] | dW0 [64][K0P] | db0 [64]
     float *r1 = red, *rb1 = r1 + 64 * NO * 64, *r0 = rb1 + 64 * NO, *rb0 = r0 + 64 * K0P;
-#pragma unroll
-    for (int p = 0; p < 4 * NO; ++p) { ab1[p] += __shfl_xor(ab1[p], 16, 64); ab1[p] += __shfl_xor(ab1[p], 32, 64); }   // bias: every lane holds the column sum
-#pragma unroll
-    for (int p = 0; p < 4; ++p) { ab0[p] += __shfl_xor(ab0[p], 16, 64); ab0[p] += __shfl_xor(ab0[p], 32, 64); }
+    finish_colsums(ab1);
+    finish_colsums(ab0);
     const int j32 = lane & 31, h32 = lane >> 5;
     for (int w = 0; w < neckw_threads(KT0, NO) / 64; ++w) {
         if (wave == w) {
@@ -849,10 +884,8 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
                     }
             }
             if (g == 0) {
-#pragma unroll
-                for (int p = 0; p < 4 * NO; ++p) rb1[16 * p + m] = (w == 0) ? ab1[p] : rb1[16 * p + m] + ab1[p];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) rb0[16 * p + m] = (w == 0) ? ab0[p] : rb0[16 * p + m] + ab0[p];
+                fold_bias(rb1, w, ab1, m);
+                fold_bias(rb0, w, ab0, m);
             }
         }
         __syncthreads();
@@ -1223,6 +1256,197 @@ __device__ __forceinline__ void mma_frag6(const Frag6 &f, const Opd<KS> &b, int 
     a0 = EMER_MF(f.h[0], b.m[s], a0); a1 = EMER_MF(f.h[1], b.m[s], a1);
     a0 = EMER_MF(f.h[0], b.h[s], a0); a1 = EMER_MF(f.h[1], b.h[s], a1);
 }
+// k-step s of a chain operand <- its two 16-feature tiles (the stages split an operand half by half, next to the matrix instructions)
+template <int KS>
+__device__ __forceinline__ void set_kstep(Opd<KS> &o, int s, const f32x4 &t0, const f32x4 &t1) {
+    const f32x4 v[2] = {t0, t1};
+    Opd<1> o1;
+    make_opd<2>(v, o1);
+    o.h[s] = o1.h[0]; o.m[s] = o1.m[0]; o.l[s] = o1.l[0];
+}
+
+// ---- What the two one-wave kernels share: everything behind their inputs.  rgb_bwdw16_kernel stages a1 / a2 / geo global -> LDS,
+// rgb_bwdwr_kernel prefetches geo in registers and recomputes a1 / a2; from the relu masks on they run the SAME stages (rgb_w_chain,
+// rgb_w_products), which is what makes their results bitwise equal.
+#define EMER_RGBW_SB() __builtin_amdgcn_sched_barrier(0)   // pins the order of the stages of the one-wave kernels; inside a stage the scheduler is free
+
+// dW1 [64][128] and dW0 [64][64] as 32 x 32 blocks (see zero_blocks); dW2 / db2 ride along as in rgb_bwd_kernel
+struct RgbWAcc {
+    f32x16 acc1[2][4], acc0[2][2];
+    float w2acc[3], b2acc;
+};
+__device__ __forceinline__ void rgb_w_zero(RgbWAcc &s) {
+    zero_blocks(s.acc1);
+    zero_blocks(s.acc0);
+    s.w2acc[0] = 0.0f; s.w2acc[1] = 0.0f; s.w2acc[2] = 0.0f; s.b2acc = 0.0f;
+}
+
+// The lane's constants.  The three matrices of the chain (W1a^T | W1g^T | W0g^T) are staged back to back at `chain` in both kernels.
+struct RgbWLane {
+    int wave, lane, m, g;
+    W3 w1a, w1g, w0;
+    SelE sel;
+    float w2a[4];               // W2^T (64 x 3) in four registers, as rgb_bwd_kernel
+    int tpr;
+    int64_t wave_id, n_waves;   // a wave takes the rays wave_id, wave_id + n_waves, ...
+    unsigned lo64, log, lo3c;   // this lane's offset inside a tile of a [.][64] tensor, of geo, of out / dout (channel clamped to 2)
+};
+__device__ __forceinline__ void rgb_w_stage_chain(u32x4 *chain, const RgbBwdWArgs &a) {
+    stage_w3(chain, 4, 2, a.w1at);
+    stage_w3(chain + w3_units(4, 2), 4, 2, a.w1gt);
+    stage_w3(chain + 2 * w3_units(4, 2), 4, 2, a.w0gt);
+}
+__device__ __forceinline__ RgbWLane rgb_w_lane(const u32x4 *chain, const RgbBwdWArgs &a) {
+    RgbWLane L;
+    L.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); L.lane = threadIdx.x & 63; L.m = L.lane & 15; L.g = L.lane >> 4;
+    L.w1a = w3_at(chain, 4, 2, L.lane); L.w1g = w3_at(chain + w3_units(4, 2), 4, 2, L.lane); L.w0 = w3_at(chain + 2 * w3_units(4, 2), 4, 2, L.lane);
+    L.sel = make_sel(L.lane);
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+        L.w2a[p] = (L.g < a.w2t.k && 16 * p + L.m < a.w2t.n) ? a.w2t.w[(16 * p + L.m) * a.w2t.sn + L.g * a.w2t.sk] : 0.0f;
+    L.tpr = a.tiles_per_ray;
+    L.wave_id = (int64_t)blockIdx.x * (kRWThreads / 64) + L.wave; L.n_waves = (int64_t)gridDim.x * (kRWThreads / 64);
+    L.lo64 = (unsigned)(L.m * 64 + 4 * L.g); L.log = (unsigned)L.m * (unsigned)a.ld_geo + 4u * L.g;
+    L.lo3c = (unsigned)(3 * L.m + (L.g < 3 ? L.g : 2));
+    return L;
+}
+
+// dgeo of a tile is STORED AT THE START OF THE NEXT TILE, right behind that tile's wait for its inputs: on this part stores count in
+// vmcnt like loads, so a store issued mid-tile is still in flight at the next `s_waitcnt vmcnt(0)` and the wave sits out its write
+// acknowledgement (measured: 90 of 420 us); issued behind the wait it has a whole tile to drain.  The values stay where the matrix
+// pipe left them (accumulator registers) in the meantime.
+__device__ __forceinline__ void rgb_w_store_dgeo(float *dgeo_prev, const f32x4 (&dgp)[4], unsigned lo64) {
+    if (dgeo_prev) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(dgeo_prev + (lo64 + 16u * p)) = dgp[p];
+    }
+}
+
+// The chain of one 16-row tile.  One wave per SIMD: whatever overlaps, overlaps inside this instruction stream.  The three GEMMs run as
+// twelve stages of twelve matrix instructions (two output tiles x one k-step x six partial products); every stage first issues the
+// NEXT stage's weight-fragment reads (the last one of a tile: the first stage of whatever follows, `wnext`), then its matrix
+// instructions, then a share of the vector work that does not depend on them -- the output layer's weight gradient next to the first
+// GEMM, the masking / splitting of d0 next to dgeo's d1 half, and next to its d0 half the caller's `side(0..3)` (rgb_bwdw16_kernel: the
+// split + transposition of the B operands a1, geo).  EMER_RGBW_SB() pins the stage order; inside a stage the scheduler is free.
+// In: fa = fragments (w1a, 0, 0), d2 = dpre2 of (row m, channel g), m2 = a2 (relu mask and operand of dW2), a1_mask(m1) fills the relu
+// mask of d0 when it is needed.  Out: d1o / d0o = dpre1 / dpre0 as chain operands, dg = dgeo, fa = fragments (wnext, 0, 0).
+template <class A1Mask, class Side>
+__device__ __forceinline__ void rgb_w_chain(RgbWAcc &st, const RgbWLane &L, Frag6 &fa, Frag6 &fb, const W3 wnext, float d2, const f32x4 (&m2)[4],
+                                            A1Mask a1_mask, Side side, Opd<2> &d1o, Opd<2> &d0o, f32x4 (&dg)[4]) {
+    const int m = L.m;
+    {
+        f32x4 d1[4];
+        zero<4>(d1);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) d1[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(L.w2a[p], d2, d1[p], 0, 0, 0);
+        relu_mask<4>(d1, m2);
+        make_opd<4>(d1, d1o);
+    }
+    EMER_RGBW_SB();
+    f32x4 d0[4];
+    zero<4>(dg); zero<4>(d0);
+    // ---- GEMM 1: d0 = W1a^T d1 (stages 0-3) next to dW2 / db2
+    ld_frag6(fb, L.w1a, 0, 1); mma_frag6<2>(fa, d1o, 0, d0[0], d0[1]);
+    st.b2acc += d2;
+    { const float dc = __shfl(d2, m, 64); st.w2acc[0] += row16_reduce_scatter(m2, dc, m); }
+    EMER_RGBW_SB();
+    ld_frag6(fa, L.w1a, 1, 0); mma_frag6<2>(fb, d1o, 0, d0[2], d0[3]);
+    { const float dc = __shfl(d2, 16 + m, 64); st.w2acc[1] += row16_reduce_scatter(m2, dc, m); }
+    EMER_RGBW_SB();
+    ld_frag6(fb, L.w1a, 1, 1); mma_frag6<2>(fa, d1o, 1, d0[0], d0[1]);
+    { const float dc = __shfl(d2, 32 + m, 64); st.w2acc[2] += row16_reduce_scatter(m2, dc, m); }
+    EMER_RGBW_SB();
+    ld_frag6(fa, L.w1g, 0, 0); mma_frag6<2>(fb, d1o, 1, d0[2], d0[3]);
+    EMER_RGBW_SB();
+    // ---- GEMM 2: dgeo += W1g^T d1 (stages 4-7) next to the mask and split of d0
+    ld_frag6(fb, L.w1g, 0, 1); mma_frag6<2>(fa, d1o, 0, dg[0], dg[1]);
+    {
+        f32x4 m1[4];
+        a1_mask(m1);
+        relu_mask<4>(d0, m1);
+    }
+    EMER_RGBW_SB();
+    ld_frag6(fa, L.w1g, 1, 0); mma_frag6<2>(fb, d1o, 0, dg[2], dg[3]);
+    set_kstep(d0o, 0, d0[0], d0[1]);
+    EMER_RGBW_SB();
+    ld_frag6(fb, L.w1g, 1, 1); mma_frag6<2>(fa, d1o, 1, dg[0], dg[1]);
+    set_kstep(d0o, 1, d0[2], d0[3]);
+    EMER_RGBW_SB();
+    ld_frag6(fa, L.w0, 0, 0); mma_frag6<2>(fb, d1o, 1, dg[2], dg[3]);
+    EMER_RGBW_SB();
+    // ---- GEMM 3: dgeo += W0g^T d0 (stages 8-11) next to the caller's side work
+    ld_frag6(fb, L.w0, 0, 1); mma_frag6<2>(fa, d0o, 0, dg[0], dg[1]);
+    side(0);
+    EMER_RGBW_SB();
+    ld_frag6(fa, L.w0, 1, 0); mma_frag6<2>(fb, d0o, 0, dg[2], dg[3]);
+    side(1);
+    EMER_RGBW_SB();
+    ld_frag6(fb, L.w0, 1, 1); mma_frag6<2>(fa, d0o, 1, dg[0], dg[1]);
+    side(2);
+    EMER_RGBW_SB();
+    ld_frag6(fa, wnext, 0, 0); mma_frag6<2>(fb, d0o, 1, dg[2], dg[3]);
+    side(3);
+    EMER_RGBW_SB();
+}
+
+// dW1 += dpre1^T [a1 | geo], dW0 += dpre0^T geo on the tile's 16 rows, as 32 x 32 blocks.  Bq: a1 features 0-31, 32-63; geo features 0-31,
+// 32-63 (rows on the reduction index); s1c / s0c += the column sums of dpre1 / dpre0 (one partial per lane group).
+__device__ __forceinline__ void rgb_w_products(RgbWAcc &st, const SelE sel, const Opd<2> &d1o, const Opd<2> &d0o, const SwP (&Bq)[4], float (&s1c)[4],
+                                               float (&s0c)[4]) {
+#pragma unroll
+    for (int P = 0; P < 2; ++P) {
+        const SwT t0 = to_rows<2>(d1o, 2 * P, sel, &s1c[2 * P]), t1 = to_rows<2>(d1o, 2 * P + 1, sel, &s1c[2 * P + 1]);
+        const SwP A = block32(t0, t1);
+        dw_blocks<4>(st.acc1[P], A, Bq);
+    }
+#pragma unroll
+    for (int P = 0; P < 2; ++P) {
+        const SwT t0 = to_rows<2>(d0o, 2 * P, sel, &s0c[2 * P]), t1 = to_rows<2>(d0o, 2 * P + 1, sel, &s0c[2 * P + 1]);
+        const SwP A = block32(t0, t1);
+        dw_blocks<2>(st.acc0[P], A, *reinterpret_cast<const SwP (*)[2]>(&Bq[2]));
+    }
+    EMER_RGBW_SB();
+}
+
+// the ray is done: s1 / s0 [ray][64] = the sums of dpre1 / dpre0 over its samples
+__device__ __forceinline__ void rgb_w_store_sums(const RgbBwdWArgs &a, const RgbWLane &L, int64_t ray, float (&s1c)[4], float (&s0c)[4]) {
+    finish_colsums(s1c);
+    finish_colsums(s0c);
+    if (L.g == 0) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { a.s1[ray * 64 + 16 * p + L.m] = s1c[p]; a.s0[ray * 64 + 16 * p + L.m] = s0c[p]; }
+    }
+}
+
+// Sum the four waves through LDS (the weights are dead) and write one coalesced partial per workgroup:
+// dW1 [64][128] | dW0 [64][64] | dW2 [3][64] | db2 [3] | pad (kRgbBwdWStride floats)
+__device__ __forceinline__ void rgb_w_epilogue(RgbWAcc &st, const RgbBwdWArgs &a, const RgbWLane &L, u32x4 *smem) {
+    const int wave = L.wave, m = L.m, g = L.g;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    constexpr int P1 = 132, P0 = 68;
+    float *r1 = reinterpret_cast<float *>(smem), *r0 = r1 + 64 * P1, *r2 = r0 + 64 * P0;
+    for (int w = 0; w < kRWThreads / 64; ++w) {
+        if (wave == w) {
+            fold_blocks<P1>(r1, w, st.acc1, L.lane);
+            fold_blocks<P0>(r0, w, st.acc0, L.lane);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r2[wave * 196 + c * 64 + 16 * (m >> 2) + 4 * g + (m & 3)] = st.w2acc[c];
+    st.b2acc = row16_sum(st.b2acc);
+    if (m == 0 && g < 3) r2[wave * 196 + 192 + g] = st.b2acc;
+    __syncthreads();
+    float *part = a.partials + (int64_t)blockIdx.x * a.stride;
+    for (int i = threadIdx.x; i < 64 * 128; i += kRWThreads) part[i] = r1[(i >> 7) * P1 + (i & 127)];
+    for (int i = threadIdx.x; i < 64 * 64; i += kRWThreads) part[64 * 128 + i] = r0[(i >> 6) * P0 + (i & 63)];
+    if ((int)threadIdx.x < 195) {
+        float t = 0.0f;
+        for (int w = 0; w < kRWThreads / 64; ++w) t += r2[w * 196 + threadIdx.x];
+        part[64 * 128 + 64 * 64 + threadIdx.x] = t;
+    }
+}
 
 // One 16-row tile at a time (no state carried between tiles), with the dW
 // products on v_mfma_f32_32x32x16_bf16: its reduction index is 16 long -- one row tile -- and one instruction covers a 32 x 32 block of
@@ -1231,57 +1455,33 @@ __device__ __forceinline__ void mma_frag6(const Frag6 &f, const Opd<KS> &b, int 
 // after ONE v_permlane16_swap_b32 per register: lanes 16-31 / 48-63 take the second tile's rows 0-3 / 8-11 from lanes 0-15 / 32-47 and
 // give the first tile's rows 4-7 / 12-15 back, which leaves lane (i, kg) with rows 8 kg .. 8 kg + 7 of its feature.
 // Per tile: 148 chain + 48 transposer (16 x 16 x 32) + 72 dW (32 x 32 x 16) instructions.  Any S % 16 == 0.
-#define EMER_RGBW_SB() __builtin_amdgcn_sched_barrier(0)   // pins the order of the stages of the one-wave kernels; inside a stage the scheduler is free
 __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdWArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    u32x4 *w1al = smem, *w1gl = w1al + w3_units(4, 2), *w0l = w1gl + w3_units(4, 2);
-    stage_w3(w1al, 4, 2, a.w1at);
-    stage_w3(w1gl, 4, 2, a.w1gt);
-    stage_w3(w0l, 4, 2, a.w0gt);
+    rgb_w_stage_chain(smem, a);
     __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
-    const W3 w1ap = w3_at(w1al, 4, 2, lane), w1gp = w3_at(w1gl, 4, 2, lane), w0p = w3_at(w0l, 4, 2, lane);
-    const SelE sel = make_sel(lane);
-    float w2a[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) w2a[p] = (g < a.w2t.k && 16 * p + m < a.w2t.n) ? a.w2t.w[(16 * p + m) * a.w2t.sn + g * a.w2t.sk] : 0.0f;
+    const RgbWLane L = rgb_w_lane(smem, a);
+    const int lane = L.lane, m = L.m, g = L.g, tpr = L.tpr;
     // per-wave staging, filled global -> LDS (lane-major: lane (m, g) of piece p holds columns 16 p + 4 g .. + 3 of row m): the next tile's
     // a2 (1024 floats, single buffer: consumed at the start of a tile) and, DOUBLE buffered, its a1 | geo (2 x 2048 floats: they are
     // consumed at the END of a tile -- as the relu mask of d0 and, read back TRANSPOSED, as the B operands of the dW products)
-    float *stg = reinterpret_cast<float *>(w0l + w3_units(4, 2)) + wave * (2048 + 3072);
+    float *stg = reinterpret_cast<float *>(smem + 3 * w3_units(4, 2)) + L.wave * (2048 + 3072);
     using gptr = const __attribute__((address_space(1))) void *;
     using lptr = __attribute__((address_space(3))) void *;
-    // dW1 [64][128] and dW0 [64][64] as 32 x 32 blocks: lane (j, h), register r = dW[32 P + 8 (r >> 2) + 4 h + (r & 3)][32 Q + j]
-    f32x16 acc1[2][4], acc0[2][2];
-#pragma unroll
-    for (int P = 0; P < 2; ++P) {
-#pragma unroll
-        for (int Q = 0; Q < 4; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[P][Q][r] = 0.0f;
-#pragma unroll
-        for (int Q = 0; Q < 2; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[P][Q][r] = 0.0f;
-    }
-    float w2acc[3] = {0.0f, 0.0f, 0.0f}, b2acc = 0.0f;
-    const int tpr = a.tiles_per_ray;
-    const int64_t wave_id = (int64_t)blockIdx.x * (kRWThreads / 64) + wave, n_waves = (int64_t)gridDim.x * (kRWThreads / 64);
-    const unsigned lo64 = (unsigned)(m * 64 + 4 * g), log = (unsigned)m * (unsigned)a.ld_geo + 4u * g;
-    const unsigned lo3c = (unsigned)(3 * m + (g < 3 ? g : 2));
+    RgbWAcc st;
+    rgb_w_zero(st);
     float yn = 0.0f, dn = 0.0f;
     auto issue = [&](int64_t ray, int j, int buf) {
         const int64_t row0 = (ray * tpr + j) * 16;
         const float *p2 = a.a2 + row0 * 64, *p1 = a.a1 + row0 * 64, *pg = a.geo + row0 * a.ld_geo;
         float *sb = stg + 1024 + 2048 * buf;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(p2 + (lo64 + 16u * p)), (lptr)(stg + 256 * p), 16, 0, 0);
+        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(p2 + (L.lo64 + 16u * p)), (lptr)(stg + 256 * p), 16, 0, 0);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(p1 + (lo64 + 16u * p)), (lptr)(sb + 256 * p), 16, 0, 0);
+        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(p1 + (L.lo64 + 16u * p)), (lptr)(sb + 256 * p), 16, 0, 0);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(pg + (log + 16u * p)), (lptr)(sb + 1024 + 256 * p), 16, 0, 0);
-        yn = (a.out + row0 * 3)[lo3c];
-        dn = (a.dout + row0 * 3)[lo3c];
+        for (int p = 0; p < 4; ++p) __builtin_amdgcn_global_load_lds((gptr)(pg + (L.log + 16u * p)), (lptr)(sb + 1024 + 256 * p), 16, 0, 0);
+        yn = (a.out + row0 * 3)[L.lo3c];
+        dn = (a.dout + row0 * 3)[L.lo3c];
     };
     // B operand of a dW product straight from the staged tile: lane (j, gg) of a transposer output holds rows 4 gg .. 4 gg + 3 of feature
     // 16 p + j -- which sits at float 256 p + 4 (row + 16 (j >> 2)) + (j & 3) of the lane-major tile.  Four strided LDS reads and two
@@ -1302,29 +1502,22 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
         nr = ray; nj = j;
         for (int i = 0; i < by; ++i) {
             int64_t r2 = nr; int j2 = nj + 1;
-            if (j2 == tpr) { j2 = 0; r2 = nr + n_waves; }
+            if (j2 == tpr) { j2 = 0; r2 = nr + L.n_waves; }
             if (r2 >= a.n_rays) break;
             nr = r2; nj = j2;
         }
     };
-    if (wave_id < a.n_rays) issue(wave_id, 0, 0);
-    // dgeo of a tile is STORED AT THE START OF THE NEXT TILE, right behind that tile's wait for its inputs: on this part stores count in
-    // vmcnt like loads, so a store issued mid-tile is still in flight at the next `s_waitcnt vmcnt(0)` and the wave sits out its write
-    // acknowledgement (measured: 90 of 420 us); issued behind the wait it has a whole tile to drain.  The values stay where the matrix
-    // pipe left them (accumulator registers) in the meantime.
-    f32x4 dgp[4];
+    if (L.wave_id < a.n_rays) issue(L.wave_id, 0, 0);
+    f32x4 dgp[4];   // dgeo of the previous tile (see rgb_w_store_dgeo)
     float *dgeo_prev = nullptr;
     Frag6 fa, fb;
-    ld_frag6(fa, w1ap, 0, 0);
-    for (int64_t ray = wave_id; ray < a.n_rays; ray += n_waves) {
+    ld_frag6(fa, L.w1a, 0, 0);
+    for (int64_t ray = L.wave_id; ray < a.n_rays; ray += L.n_waves) {
         float s1c[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s0c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < tpr; ++j) {
             float *dgeo = a.dgeo + ((ray * tpr + j) * 16) * 64;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (dgeo_prev) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(dgeo_prev + (lo64 + 16u * p)) = dgp[p];
-            }
+            rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
             f32x4 m2[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) m2[p] = *reinterpret_cast<const f32x4 *>(stg + 256 * p + 4 * lane);
@@ -1337,156 +1530,37 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
                 issue(nr, nj, buf ^ 1);
             }
             buf ^= 1;
-            // Order of the tile body.  One wave per SIMD: whatever overlaps, overlaps inside this instruction stream.  The three GEMMs of the
-            // chain run as twelve stages of twelve matrix instructions (two output tiles x one k-step x six partial products); every stage
-            // first issues the NEXT stage's weight-fragment reads (the last one of a tile: the next tile's first), then its matrix
-            // instructions, then a share of the vector work that does not depend on them -- the output layer's weight gradient next to the
-            // first GEMM, the masking / splitting of d0 next to dgeo's d1 half, the split + transposition of the B operands (a1, geo) next to
-            // its d0 half.  EMER_RGBW_SB() pins the stage order; inside a stage the scheduler is free.
             Opd<2> d1o, d0o;
-            {
-                f32x4 d1[4];
-                zero<4>(d1);
+            f32x4 dg[4];
+            SwP Bq[4];
+            rgb_w_chain(st, L, fa, fb, L.w1a, d2, m2,
+                        [&](f32x4 (&m1)[4]) {   // a1 from the staged tile, read only here: the mask is not live across GEMM 1
 #pragma unroll
-                for (int p = 0; p < 4; ++p) d1[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2a[p], d2, d1[p], 0, 0, 0);
-                relu_mask<4>(d1, m2);
-                make_opd<4>(d1, d1o);
-            }
-            EMER_RGBW_SB();
-            f32x4 dg[4], d0[4];
-            zero<4>(dg); zero<4>(d0);
-            SwP Bq[4];   // a1 features 0-31, 32-63; geo features 0-31, 32-63 (rows on the reduction index, 32-feature blocks)
-            // ---- GEMM 1: d0 = W1a^T d1 (stages 0-3) next to dW2 / db2
-            ld_frag6(fb, w1ap, 0, 1); mma_frag6<2>(fa, d1o, 0, d0[0], d0[1]);
-            b2acc += d2;
-            { const float dc = __shfl(d2, m, 64); w2acc[0] += row16_reduce_scatter(m2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1ap, 1, 0); mma_frag6<2>(fb, d1o, 0, d0[2], d0[3]);
-            { const float dc = __shfl(d2, 16 + m, 64); w2acc[1] += row16_reduce_scatter(m2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fb, w1ap, 1, 1); mma_frag6<2>(fa, d1o, 1, d0[0], d0[1]);
-            { const float dc = __shfl(d2, 32 + m, 64); w2acc[2] += row16_reduce_scatter(m2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1gp, 0, 0); mma_frag6<2>(fb, d1o, 1, d0[2], d0[3]);
-            EMER_RGBW_SB();
-            // ---- GEMM 2: dgeo += W1g^T d1 (stages 4-7) next to the mask and split of d0
-            ld_frag6(fb, w1gp, 0, 1); mma_frag6<2>(fa, d1o, 0, dg[0], dg[1]);
-            {
-                f32x4 m1[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) m1[p] = *reinterpret_cast<const f32x4 *>(sb + 256 * p + 4 * lane);
-                relu_mask<4>(d0, m1);
-            }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1gp, 1, 0); mma_frag6<2>(fb, d1o, 0, dg[2], dg[3]);
-            {   // k-step 0 of the split operand = tiles 0, 1; k-step 1 = tiles 2, 3
-                f32x4 v[2] = {d0[0], d0[1]};
-                Opd<1> o1;
-                make_opd<2>(v, o1);
-                d0o.h[0] = o1.h[0]; d0o.m[0] = o1.m[0]; d0o.l[0] = o1.l[0];
-            }
-            EMER_RGBW_SB();
-            ld_frag6(fb, w1gp, 1, 1); mma_frag6<2>(fa, d1o, 1, dg[0], dg[1]);
-            {
-                f32x4 v[2] = {d0[2], d0[3]};
-                Opd<1> o1;
-                make_opd<2>(v, o1);
-                d0o.h[1] = o1.h[0]; d0o.m[1] = o1.m[0]; d0o.l[1] = o1.l[0];
-            }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w0p, 0, 0); mma_frag6<2>(fb, d1o, 1, dg[2], dg[3]);
-            EMER_RGBW_SB();
-            // ---- GEMM 3: dgeo += W0g^T d0 (stages 8-11) next to the B operands of the dW products
-            ld_frag6(fb, w0p, 0, 1); mma_frag6<2>(fa, d0o, 0, dg[0], dg[1]);
-            Bq[0] = block32(b_tile(sb, 0), b_tile(sb, 1));
-            EMER_RGBW_SB();
-            ld_frag6(fa, w0p, 1, 0); mma_frag6<2>(fb, d0o, 0, dg[2], dg[3]);
-            Bq[1] = block32(b_tile(sb, 2), b_tile(sb, 3));
-            EMER_RGBW_SB();
-            ld_frag6(fb, w0p, 1, 1); mma_frag6<2>(fa, d0o, 1, dg[0], dg[1]);
-            Bq[2] = block32(b_tile(sb + 1024, 0), b_tile(sb + 1024, 1));
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1ap, 0, 0); mma_frag6<2>(fb, d0o, 1, dg[2], dg[3]);   // (fa: the next tile's first stage)
-            Bq[3] = block32(b_tile(sb + 1024, 2), b_tile(sb + 1024, 3));
-            EMER_RGBW_SB();
+                            for (int p = 0; p < 4; ++p) m1[p] = *reinterpret_cast<const f32x4 *>(sb + 256 * p + 4 * lane);
+                        },
+                        [&](int k) {   // the B operands of the dW products: a1 (k = 0, 1), geo (k = 2, 3)
+                            const float *t = sb + 1024 * (k >> 1);
+                            Bq[k] = block32(b_tile(t, 2 * (k & 1)), b_tile(t, 2 * (k & 1) + 1));
+                        },
+                        d1o, d0o, dg);
 #pragma unroll
             for (int p = 0; p < 4; ++p) dgp[p] = dg[p];
             dgeo_prev = dgeo;
             EMER_RGBW_SB();
-            // ---- dW1 += dpre1^T [a1 | geo], dW0 += dpre0^T geo on this tile's 16 rows, as 32 x 32 blocks
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const SwT t0 = to_rows<2>(d1o, 2 * P, sel, &s1c[2 * P]), t1 = to_rows<2>(d1o, 2 * P + 1, sel, &s1c[2 * P + 1]);
-                const SwP A = block32(t0, t1);
-                dw_blocks<4>(acc1[P], A, Bq);
-            }
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const SwT t0 = to_rows<2>(d0o, 2 * P, sel, &s0c[2 * P]), t1 = to_rows<2>(d0o, 2 * P + 1, sel, &s0c[2 * P + 1]);
-                const SwP A = block32(t0, t1);
-                dw_blocks<2>(acc0[P], A, *reinterpret_cast<const SwP (*)[2]>(&Bq[2]));
-            }
-            EMER_RGBW_SB();
+            rgb_w_products(st, L.sel, d1o, d0o, Bq, s1c, s0c);
         }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            s1c[p] += __shfl_xor(s1c[p], 16, 64); s1c[p] += __shfl_xor(s1c[p], 32, 64);
-            s0c[p] += __shfl_xor(s0c[p], 16, 64); s0c[p] += __shfl_xor(s0c[p], 32, 64);
-            if (g == 0) { a.s1[ray * 64 + 16 * p + m] = s1c[p]; a.s0[ray * 64 + 16 * p + m] = s0c[p]; }
-        }
+        rgb_w_store_sums(a, L, ray, s1c, s0c);
     }
-    if (dgeo_prev) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(dgeo_prev + (lo64 + 16u * p)) = dgp[p];
-    }
-    // ---- sum the four waves through LDS (the weights are dead), one coalesced partial per workgroup (the paired kernel's layout)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    constexpr int P1 = 132, P0 = 68;
-    float *r1 = reinterpret_cast<float *>(smem), *r0 = r1 + 64 * P1, *r2 = r0 + 64 * P0;
-    const int j32 = lane & 31, h32 = lane >> 5;
-    for (int w = 0; w < kRWThreads / 64; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-#pragma unroll
-                for (int Q = 0; Q < 4; ++Q)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float *q = r1 + (32 * P + 8 * (r >> 2) + 4 * h32 + (r & 3)) * P1 + 32 * Q + j32;
-                        *q = (w == 0) ? acc1[P][Q][r] : *q + acc1[P][Q][r];
-                    }
-#pragma unroll
-                for (int Q = 0; Q < 2; ++Q)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float *q = r0 + (32 * P + 8 * (r >> 2) + 4 * h32 + (r & 3)) * P0 + 32 * Q + j32;
-                        *q = (w == 0) ? acc0[P][Q][r] : *q + acc0[P][Q][r];
-                    }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) r2[wave * 196 + c * 64 + 16 * (m >> 2) + 4 * g + (m & 3)] = w2acc[c];
-    b2acc = row16_sum(b2acc);
-    if (m == 0 && g < 3) r2[wave * 196 + 192 + g] = b2acc;
-    __syncthreads();
-    float *part = a.partials + (int64_t)blockIdx.x * a.stride;
-    for (int i = threadIdx.x; i < 64 * 128; i += kRWThreads) part[i] = r1[(i >> 7) * P1 + (i & 127)];
-    for (int i = threadIdx.x; i < 64 * 64; i += kRWThreads) part[64 * 128 + i] = r0[(i >> 6) * P0 + (i & 63)];
-    if ((int)threadIdx.x < 195) {
-        float t = 0.0f;
-        for (int w = 0; w < kRWThreads / 64; ++w) t += r2[w * 196 + threadIdx.x];
-        part[64 * 128 + 64 * 64 + threadIdx.x] = t;
-    }
+    rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
+    rgb_w_epilogue(st, a, L, smem);
 }
 
 // ---- [r6] the same backward with a1 / a2 RECOMPUTED from geo and the per-ray pre-activations: the forward (field_fwd_kernel / rgb_fwd_kernel
 // with a1 = a2 = NULL) then stores nothing but geo and the colours, and this kernel reads geo (256 B / sample) instead of geo + a1 + a2
 // (768 B / sample): 1.07 GB of HBM traffic per million samples and step gone.  a1 = relu(W0g geo + rb0), a2 = relu(W1g geo + W1a a1 + rb1)
 // are evaluated with the forward's fragments in the forward's order per accumulator (rb, then k-step 0, then k-step 1; for a2: the geo
-// part first), so they are BITWISE the forward's values and every result of this kernel is bitwise rgb_bwdw16_kernel's.
+// part first), so they are BITWISE the forward's values; behind them the kernel runs rgb_bwdw16_kernel's own stages, so every result is
+// bitwise that kernel's.
 //   * LDS: six 64 x 64 weight matrices as bf16x3 fragments (W0g, W1a, W1g for the recomputation, their transposes for the chain) = 144 KB,
 //     plus 1 KB per wave for the per-ray pre-activations of the current and of the next ray (global -> LDS, 4 B per lane).  No room is
 //     left for staging tiles, and none is needed: geo is the only per-sample input; the next tile's 16 floats per lane are prefetched in
@@ -1495,17 +1569,9 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
 //     recomputation has split anyway, through the matrix-core transposer (to_rows: 3 instructions per 16-feature tile, exact) -- the
 //     same bits b_tile() reads back from the staged tile in rgb_bwdw16_kernel (the 3-term split is elementwise).
 //   * Per tile: 144 (recomputation) + 148 (chain) + 48 (transposer: dpre1, dpre0, a1, geo) 16 x 16 x 32 instructions + 72 of 32 x 32 x 16.
-struct RgbBwdRArgs {
-    const float *dout, *out;            // [n][3]
-    const float *geo; int64_t ld_geo;   // [n][>= 64] the head's per-sample input
+struct RgbBwdRArgs : RgbBwdWArgs {           // a1: the forward's stored a1 (A1_STORED) or null; a2 is not read
     const float *rb0, *rb1; int64_t ld_rb;   // [rays][64] per-ray pre-activations of layers 0 / 1 (bias included), as the forward's
-    int32_t tiles_per_ray; int64_t n_rays;
-    const float *a1;                    // [n][64] the forward's stored a1 (A1_STORED) or null
-    WSrc w0g, w1a, w1g;                 // forward views (RgbFwdArgs)
-    WSrc w2t, w1at, w1gt, w0gt;         // transposed views (RgbBwdArgs)
-    float *dgeo;                        // [n][64]
-    float *s1, *s0;                     // [rays][64]
-    float *partials; int64_t stride;    // as RgbBwdWArgs
+    WSrc w0g, w1a, w1g;                      // forward views (RgbFwdArgs)
 };
 
 // A1_STORED: the cheaper half -- a1 comes from the forward's store (prefetched in registers like geo), only a2 is recomputed (96 instead of
@@ -1513,43 +1579,22 @@ struct RgbBwdRArgs {
 template <bool A1_STORED>
 __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    u32x4 *w0fl = smem, *w1afl = w0fl + w3_units(4, 2), *w1gfl = w1afl + w3_units(4, 2);
-    u32x4 *w1al = w1gfl + w3_units(4, 2), *w1gl = w1al + w3_units(4, 2), *w0l = w1gl + w3_units(4, 2);
+    u32x4 *w0fl = smem, *w1afl = w0fl + w3_units(4, 2), *w1gfl = w1afl + w3_units(4, 2), *chain = w1gfl + w3_units(4, 2);
     if (!A1_STORED) stage_w3(w0fl, 4, 2, a.w0g);
     stage_w3(w1afl, 4, 2, a.w1a);
     stage_w3(w1gfl, 4, 2, a.w1g);
-    stage_w3(w1al, 4, 2, a.w1at);
-    stage_w3(w1gl, 4, 2, a.w1gt);
-    stage_w3(w0l, 4, 2, a.w0gt);
+    rgb_w_stage_chain(chain, a);
     __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
+    const RgbWLane L = rgb_w_lane(chain, a);
+    const int lane = L.lane, g = L.g, tpr = L.tpr;
+    const SelE sel = L.sel;
     const W3 w0f = w3_at(w0fl, 4, 2, lane), w1af = w3_at(w1afl, 4, 2, lane), w1gf = w3_at(w1gfl, 4, 2, lane);
-    const W3 w1ap = w3_at(w1al, 4, 2, lane), w1gp = w3_at(w1gl, 4, 2, lane), w0p = w3_at(w0l, 4, 2, lane);
-    const SelE sel = make_sel(lane);
-    float w2a[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) w2a[p] = (g < a.w2t.k && 16 * p + m < a.w2t.n) ? a.w2t.w[(16 * p + m) * a.w2t.sn + g * a.w2t.sk] : 0.0f;
     // per wave: [parity][rb0 (64) | rb1 (64)] floats
-    float *rbl = reinterpret_cast<float *>(w0l + w3_units(4, 2)) + wave * 256;
+    float *rbl = reinterpret_cast<float *>(chain + 3 * w3_units(4, 2)) + L.wave * 256;
     using gptr = const __attribute__((address_space(1))) void *;
     using lptr = __attribute__((address_space(3))) void *;
-    f32x16 acc1[2][4], acc0[2][2];
-#pragma unroll
-    for (int P = 0; P < 2; ++P) {
-#pragma unroll
-        for (int Q = 0; Q < 4; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[P][Q][r] = 0.0f;
-#pragma unroll
-        for (int Q = 0; Q < 2; ++Q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[P][Q][r] = 0.0f;
-    }
-    float w2acc[3] = {0.0f, 0.0f, 0.0f}, b2acc = 0.0f;
-    const int tpr = a.tiles_per_ray;
-    const int64_t wave_id = (int64_t)blockIdx.x * (kRWThreads / 64) + wave, n_waves = (int64_t)gridDim.x * (kRWThreads / 64);
-    const unsigned lo64 = (unsigned)(m * 64 + 4 * g), log = (unsigned)m * (unsigned)a.ld_geo + 4u * g;
-    const unsigned lo3c = (unsigned)(3 * m + (g < 3 ? g : 2));
+    RgbWAcc st;
+    rgb_w_zero(st);
     float yn = 0.0f, dn = 0.0f;
     f32x4 xg[4];   // the NEXT tile's geo in chain layout (lane (m, g): columns 16 p + 4 g .. + 3 of row m)
     f32x4 ag[4];   // ... and its stored a1 (A1_STORED)
@@ -1558,14 +1603,14 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
         const int64_t row0 = (ray * tpr + j) * 16;
         const float *pg = a.geo + row0 * a.ld_geo;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) xg[p] = *reinterpret_cast<const f32x4 *>(pg + (log + 16u * p));
+        for (int p = 0; p < 4; ++p) xg[p] = *reinterpret_cast<const f32x4 *>(pg + (L.log + 16u * p));
         if (A1_STORED) {
             const float *pa = a.a1 + row0 * 64;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) ag[p] = *reinterpret_cast<const f32x4 *>(pa + (lo64 + 16u * p));
+            for (int p = 0; p < 4; ++p) ag[p] = *reinterpret_cast<const f32x4 *>(pa + (L.lo64 + 16u * p));
         }
-        yn = (a.out + row0 * 3)[lo3c];
-        dn = (a.dout + row0 * 3)[lo3c];
+        yn = (a.out + row0 * 3)[L.lo3c];
+        dn = (a.dout + row0 * 3)[L.lo3c];
         if (j == 0) {   // (wave-uniform) first tile of a ray: its pre-activations, 64 + 64 floats, one per lane each, into buffer `par`
             if (!A1_STORED) __builtin_amdgcn_global_load_lds((gptr)(a.rb0 + ray * a.ld_rb + lane), (lptr)(rbl + 128 * par), 4, 0, 0);
             __builtin_amdgcn_global_load_lds((gptr)(a.rb1 + ray * a.ld_rb + lane), (lptr)(rbl + 128 * par + 64), 4, 0, 0);
@@ -1573,24 +1618,21 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
     };
     auto advance = [&](int64_t ray, int j, int64_t &nr, int &nj) {   // the next tile of this wave's sequence (clamped at its end)
         nr = ray; nj = j + 1;
-        if (nj == tpr) { nj = 0; nr = ray + n_waves; }
+        if (nj == tpr) { nj = 0; nr = ray + L.n_waves; }
         if (nr >= a.n_rays) { nr = ray; nj = j; }
     };
-    if (wave_id < a.n_rays) issue(wave_id, 0, 0);
-    f32x4 dgp[4];
+    if (L.wave_id < a.n_rays) issue(L.wave_id, 0, 0);
+    f32x4 dgp[4];   // dgeo of the previous tile (see rgb_w_store_dgeo)
     float *dgeo_prev = nullptr;
     Frag6 fa, fb;
     const W3 wfirst = A1_STORED ? w1gf : w0f;   // the matrix of a tile's first stage
     ld_frag6(fa, wfirst, 0, 0);
-    for (int64_t ray = wave_id; ray < a.n_rays; ray += n_waves) {
+    for (int64_t ray = L.wave_id; ray < a.n_rays; ray += L.n_waves) {
         float s1c[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s0c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < tpr; ++j) {
             float *dgeo = a.dgeo + ((ray * tpr + j) * 16) * 64;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (dgeo_prev) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(dgeo_prev + (lo64 + 16u * p)) = dgp[p];
-            }
+            rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
             f32x4 x[4], a1[4], a2[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) { x[p] = xg[p]; if (A1_STORED) a1[p] = ag[p]; }
@@ -1608,22 +1650,12 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
             SwP Bq[4];   // a1 features 0-31, 32-63; geo features 0-31, 32-63 (rows on the reduction index, 32-feature blocks)
             if constexpr (A1_STORED) {
                 // ---- a2 = relu(W1g x + W1a a1 + rb1) with a1 from the forward's store: four stages on x, four on a1
-                {
-                    f32x4 v[2] = {x[0], x[1]};
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    xo.h[0] = o1.h[0]; xo.m[0] = o1.m[0]; xo.l[0] = o1.l[0];
-                }
+                set_kstep(xo, 0, x[0], x[1]);
 #pragma unroll
                 for (int p = 0; p < 4; ++p) a2[p] = *reinterpret_cast<const f32x4 *>(rb + 64 + 16 * p + 4 * g);
                 EMER_RGBW_SB();
                 ld_frag6(fb, w1gf, 0, 1); mma_frag6<2>(fa, xo, 0, a2[0], a2[1]);
-                {
-                    f32x4 v[2] = {x[2], x[3]};
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    xo.h[1] = o1.h[0]; xo.m[1] = o1.m[0]; xo.l[1] = o1.l[0];
-                }
+                set_kstep(xo, 1, x[2], x[3]);
                 EMER_RGBW_SB();
                 ld_frag6(fa, w1gf, 1, 0); mma_frag6<2>(fb, xo, 0, a2[2], a2[3]);
                 make_opd<4>(a1, ho);
@@ -1642,15 +1674,10 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                 EMER_RGBW_SB();
                 ld_frag6(fb, w1af, 1, 1); mma_frag6<2>(fa, ho, 1, a2[0], a2[1]);
                 EMER_RGBW_SB();
-                ld_frag6(fa, w1ap, 0, 0); mma_frag6<2>(fb, ho, 1, a2[2], a2[3]);   // (fa: the chain's first stage)
+                ld_frag6(fa, L.w1a, 0, 0); mma_frag6<2>(fb, ho, 1, a2[2], a2[3]);   // (fa: the chain's first stage)
                 EMER_RGBW_SB();
             } else {
-                {
-                    f32x4 v[2] = {x[0], x[1]};
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    xo.h[0] = o1.h[0]; xo.m[0] = o1.m[0]; xo.l[0] = o1.l[0];
-                }
+                set_kstep(xo, 0, x[0], x[1]);
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     a1[p] = *reinterpret_cast<const f32x4 *>(rb + 16 * p + 4 * g);
@@ -1658,12 +1685,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                 }
                 EMER_RGBW_SB();
                 ld_frag6(fb, w1gf, 0, 0); mma_frag6<2>(fa, xo, 0, a1[0], a1[1]);
-                {
-                    f32x4 v[2] = {x[2], x[3]};
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    xo.h[1] = o1.h[0]; xo.m[1] = o1.m[0]; xo.l[1] = o1.l[0];
-                }
+                set_kstep(xo, 1, x[2], x[3]);
                 EMER_RGBW_SB();
                 ld_frag6(fa, w0f, 0, 1); mma_frag6<2>(fb, xo, 0, a2[0], a2[1]);
                 EMER_RGBW_SB();
@@ -1678,9 +1700,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                     f32x4 v[2] = {a1[0], a1[1]};
                     relu<2>(v);
                     a1[0] = v[0]; a1[1] = v[1];
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    ho.h[0] = o1.h[0]; ho.m[0] = o1.m[0]; ho.l[0] = o1.l[0];
+                    set_kstep(ho, 0, v[0], v[1]);
                 }
                 EMER_RGBW_SB();
                 ld_frag6(fb, w1gf, 1, 1); mma_frag6<2>(fa, xo, 1, a1[2], a1[3]);
@@ -1690,9 +1710,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                     f32x4 v[2] = {a1[2], a1[3]};
                     relu<2>(v);
                     a1[2] = v[0]; a1[3] = v[1];
-                    Opd<1> o1;
-                    make_opd<2>(v, o1);
-                    ho.h[1] = o1.h[0]; ho.m[1] = o1.m[0]; ho.l[1] = o1.l[0];
+                    set_kstep(ho, 1, v[0], v[1]);
                 }
                 EMER_RGBW_SB();
                 ld_frag6(fb, w1af, 0, 1); mma_frag6<2>(fa, ho, 0, a2[0], a2[1]);
@@ -1704,140 +1722,31 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                 ld_frag6(fb, w1af, 1, 1); mma_frag6<2>(fa, ho, 1, a2[0], a2[1]);
                 Bq[0] = block32(to_rows<2>(ho, 0, sel), to_rows<2>(ho, 1, sel));
                 EMER_RGBW_SB();
-                ld_frag6(fa, w1ap, 0, 0); mma_frag6<2>(fb, ho, 1, a2[2], a2[3]);   // (fa: the chain's first stage)
+                ld_frag6(fa, L.w1a, 0, 0); mma_frag6<2>(fb, ho, 1, a2[2], a2[3]);   // (fa: the chain's first stage)
                 Bq[1] = block32(to_rows<2>(ho, 2, sel), to_rows<2>(ho, 3, sel));
                 EMER_RGBW_SB();
             }
             relu<4>(a2);
-            // ---- the chain, as rgb_bwdw16_kernel (a2 / a1 from registers instead of the staged tile)
+            // ---- the chain: a2 / a1 from registers, the B operands are ready, so no side work rides on its last stages
             Opd<2> d1o, d0o;
-            {
-                f32x4 d1[4];
-                zero<4>(d1);
+            f32x4 dg[4];
+            rgb_w_chain(st, L, fa, fb, wfirst, d2, a2,
+                        [&](f32x4 (&m1)[4]) {
 #pragma unroll
-                for (int p = 0; p < 4; ++p) d1[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2a[p], d2, d1[p], 0, 0, 0);
-                relu_mask<4>(d1, a2);
-                make_opd<4>(d1, d1o);
-            }
-            EMER_RGBW_SB();
-            f32x4 dg[4], d0[4];
-            zero<4>(dg); zero<4>(d0);
-            // ---- GEMM 1: d0 = W1a^T d1 (stages 0-3) next to dW2 / db2
-            ld_frag6(fb, w1ap, 0, 1); mma_frag6<2>(fa, d1o, 0, d0[0], d0[1]);
-            b2acc += d2;
-            { const float dc = __shfl(d2, m, 64); w2acc[0] += row16_reduce_scatter(a2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1ap, 1, 0); mma_frag6<2>(fb, d1o, 0, d0[2], d0[3]);
-            { const float dc = __shfl(d2, 16 + m, 64); w2acc[1] += row16_reduce_scatter(a2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fb, w1ap, 1, 1); mma_frag6<2>(fa, d1o, 1, d0[0], d0[1]);
-            { const float dc = __shfl(d2, 32 + m, 64); w2acc[2] += row16_reduce_scatter(a2, dc, m); }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1gp, 0, 0); mma_frag6<2>(fb, d1o, 1, d0[2], d0[3]);
-            EMER_RGBW_SB();
-            // ---- GEMM 2: dgeo += W1g^T d1 (stages 4-7) next to the mask and split of d0
-            ld_frag6(fb, w1gp, 0, 1); mma_frag6<2>(fa, d1o, 0, dg[0], dg[1]);
-            relu_mask<4>(d0, a1);
-            EMER_RGBW_SB();
-            ld_frag6(fa, w1gp, 1, 0); mma_frag6<2>(fb, d1o, 0, dg[2], dg[3]);
-            {
-                f32x4 v[2] = {d0[0], d0[1]};
-                Opd<1> o1;
-                make_opd<2>(v, o1);
-                d0o.h[0] = o1.h[0]; d0o.m[0] = o1.m[0]; d0o.l[0] = o1.l[0];
-            }
-            EMER_RGBW_SB();
-            ld_frag6(fb, w1gp, 1, 1); mma_frag6<2>(fa, d1o, 1, dg[0], dg[1]);
-            {
-                f32x4 v[2] = {d0[2], d0[3]};
-                Opd<1> o1;
-                make_opd<2>(v, o1);
-                d0o.h[1] = o1.h[0]; d0o.m[1] = o1.m[0]; d0o.l[1] = o1.l[0];
-            }
-            EMER_RGBW_SB();
-            ld_frag6(fa, w0p, 0, 0); mma_frag6<2>(fb, d1o, 1, dg[2], dg[3]);
-            EMER_RGBW_SB();
-            // ---- GEMM 3: dgeo += W0g^T d0 (stages 8-11)
-            ld_frag6(fb, w0p, 0, 1); mma_frag6<2>(fa, d0o, 0, dg[0], dg[1]);
-            EMER_RGBW_SB();
-            ld_frag6(fa, w0p, 1, 0); mma_frag6<2>(fb, d0o, 0, dg[2], dg[3]);
-            EMER_RGBW_SB();
-            ld_frag6(fb, w0p, 1, 1); mma_frag6<2>(fa, d0o, 1, dg[0], dg[1]);
-            EMER_RGBW_SB();
-            ld_frag6(fa, wfirst, 0, 0); mma_frag6<2>(fb, d0o, 1, dg[2], dg[3]);   // (fa: the next tile's first stage)
-            EMER_RGBW_SB();
+                            for (int p = 0; p < 4; ++p) m1[p] = a1[p];
+                        },
+                        [](int) {}, d1o, d0o, dg);
 #pragma unroll
             for (int p = 0; p < 4; ++p) dgp[p] = dg[p];
             dgeo_prev = dgeo;
             EMER_RGBW_SB();
-            // ---- dW1 += dpre1^T [a1 | geo], dW0 += dpre0^T geo on this tile's 16 rows, as 32 x 32 blocks
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const SwT t0 = to_rows<2>(d1o, 2 * P, sel, &s1c[2 * P]), t1 = to_rows<2>(d1o, 2 * P + 1, sel, &s1c[2 * P + 1]);
-                const SwP A = block32(t0, t1);
-                dw_blocks<4>(acc1[P], A, Bq);
-            }
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const SwT t0 = to_rows<2>(d0o, 2 * P, sel, &s0c[2 * P]), t1 = to_rows<2>(d0o, 2 * P + 1, sel, &s0c[2 * P + 1]);
-                const SwP A = block32(t0, t1);
-                dw_blocks<2>(acc0[P], A, *reinterpret_cast<const SwP (*)[2]>(&Bq[2]));
-            }
-            EMER_RGBW_SB();
+            rgb_w_products(st, sel, d1o, d0o, Bq, s1c, s0c);
         }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            s1c[p] += __shfl_xor(s1c[p], 16, 64); s1c[p] += __shfl_xor(s1c[p], 32, 64);
-            s0c[p] += __shfl_xor(s0c[p], 16, 64); s0c[p] += __shfl_xor(s0c[p], 32, 64);
-            if (g == 0) { a.s1[ray * 64 + 16 * p + m] = s1c[p]; a.s0[ray * 64 + 16 * p + m] = s0c[p]; }
-        }
+        rgb_w_store_sums(a, L, ray, s1c, s0c);
         rpar ^= 1;
     }
-    if (dgeo_prev) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(dgeo_prev + (lo64 + 16u * p)) = dgp[p];
-    }
-    // ---- sum the four waves through LDS (the weights are dead), one coalesced partial per workgroup (rgb_bwdw16_kernel's layout)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    constexpr int P1 = 132, P0 = 68;
-    float *r1 = reinterpret_cast<float *>(smem), *r0 = r1 + 64 * P1, *r2 = r0 + 64 * P0;
-    const int j32 = lane & 31, h32 = lane >> 5;
-    for (int w = 0; w < kRWThreads / 64; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-#pragma unroll
-                for (int Q = 0; Q < 4; ++Q)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float *q = r1 + (32 * P + 8 * (r >> 2) + 4 * h32 + (r & 3)) * P1 + 32 * Q + j32;
-                        *q = (w == 0) ? acc1[P][Q][r] : *q + acc1[P][Q][r];
-                    }
-#pragma unroll
-                for (int Q = 0; Q < 2; ++Q)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float *q = r0 + (32 * P + 8 * (r >> 2) + 4 * h32 + (r & 3)) * P0 + 32 * Q + j32;
-                        *q = (w == 0) ? acc0[P][Q][r] : *q + acc0[P][Q][r];
-                    }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) r2[wave * 196 + c * 64 + 16 * (m >> 2) + 4 * g + (m & 3)] = w2acc[c];
-    b2acc = row16_sum(b2acc);
-    if (m == 0 && g < 3) r2[wave * 196 + 192 + g] = b2acc;
-    __syncthreads();
-    float *part = a.partials + (int64_t)blockIdx.x * a.stride;
-    for (int i = threadIdx.x; i < 64 * 128; i += kRWThreads) part[i] = r1[(i >> 7) * P1 + (i & 127)];
-    for (int i = threadIdx.x; i < 64 * 64; i += kRWThreads) part[64 * 128 + i] = r0[(i >> 6) * P0 + (i & 63)];
-    if ((int)threadIdx.x < 195) {
-        float t = 0.0f;
-        for (int w = 0; w < kRWThreads / 64; ++w) t += r2[w * 196 + threadIdx.x];
-        part[64 * 128 + 64 * 64 + threadIdx.x] = t;
-    }
+    rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
+    rgb_w_epilogue(st, a, L, smem);
 }
 
 // ------------------------------------------------------------------------ density MLP backward with its weight gradients
@@ -2261,11 +2170,7 @@ __global__ __launch_bounds__((rmlp_w_threads<NL, NTO>()), (rmlp_w_threads<NL, NT
             f32x4 h[4];
             init_bias<4>(b0l, g, h);
             tgemm<KS0, 4, false>(w0fp, xo, h);
-#pragma unroll
-            for (int b = 0; b < KT0; ++b) {   // operand of dW0, needed at the end of the tile: parked in LDS
-                const SwT t = to_rows<KS0>(xo, b, sel);
-                park[(3 * b + 0) * 64] = t.h; park[(3 * b + 1) * 64] = t.m; park[(3 * b + 2) * 64] = t.l;
-            }
+            park_rows<KT0>(park, xo, sel);   // operand of dW0
 #pragma unroll
             for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -2383,13 +2288,9 @@ __global__ __launch_bounds__((rmlp_w_threads<NL, NTO>()), (rmlp_w_threads<NL, NT
     constexpr int NLR = 16 * NTO;   // rows of dW_last in the reduction buffer
     float *red = reinterpret_cast<float *>(smem);   // dWl [NLR][64] | dbl [NLR] | dW1 [64][64] | db1 [64] | dW0 [64][K0P] | db0 [64]
     float *rl = red, *rbl = rl + NLR * 64, *r1 = rbl + NLR, *rb1 = r1 + (NL == 3 ? 64 * 64 : 0), *r0 = rb1 + (NL == 3 ? 64 : 0), *rb0 = r0 + 64 * K0P;
-#pragma unroll
-    for (int p = 0; p < NTO; ++p) { abl[p] += __shfl_xor(abl[p], 16, 64); abl[p] += __shfl_xor(abl[p], 32, 64); }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        ab1[p] += __shfl_xor(ab1[p], 16, 64); ab1[p] += __shfl_xor(ab1[p], 32, 64);
-        ab0[p] += __shfl_xor(ab0[p], 16, 64); ab0[p] += __shfl_xor(ab0[p], 32, 64);
-    }
+    finish_colsums(abl);
+    if constexpr (NL == 3) finish_colsums(ab1);
+    finish_colsums(ab0);
     const int j32 = lane & 31, h32 = lane >> 5;
     for (int w = 0; w < NW; ++w) {
         if (wave == w) {
@@ -2433,13 +2334,9 @@ __global__ __launch_bounds__((rmlp_w_threads<NL, NTO>()), (rmlp_w_threads<NL, NT
                     }
             }
             if (g == 0) {
-#pragma unroll
-                for (int p = 0; p < NTO; ++p) rbl[16 * p + m] = (w == 0) ? abl[p] : rbl[16 * p + m] + abl[p];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    if (NL == 3) rb1[16 * p + m] = (w == 0) ? ab1[p] : rb1[16 * p + m] + ab1[p];
-                    rb0[16 * p + m] = (w == 0) ? ab0[p] : rb0[16 * p + m] + ab0[p];
-                }
+                fold_bias(rbl, w, abl, m);
+                if constexpr (NL == 3) fold_bias(rb1, w, ab1, m);
+                fold_bias(rb0, w, ab0, m);
             }
         }
         __syncthreads();
@@ -2786,6 +2683,39 @@ extern "C" int64_t emer_rgb_head_bwd_fused_workspace(int64_t n_rays, int32_t sam
     if (n_rays <= 0 || !emer_rgb_head_bwd_fused_supported(samples_per_ray)) return 0;
     return (int64_t)rgb_bwdw_grid(n_rays) * kRgbBwdWStride;
 }
+// What emer_rgb_head_bwd_fused and emer_rgb_head_bwd_recompute share: the checks (`own_ptrs` / `own_ld`: the entry point's own pointers and
+// leading dimensions), the common kernel arguments with the transposed weight views, the grid and the reduction of the workgroups'
+// partials.  launch(grid, stream) completes `a` and starts the entry point's kernel.
+template <class Launch>
+static int rgb_bwdw_run(const char *who, RgbBwdWArgs &a, bool own_ptrs, bool own_ld, const float *dout, const float *out, const float *geo,
+                        int64_t ld_geo, int64_t n_rays, int32_t samples_per_ray, int32_t kh, const float *w0, const float *w1, const float *w2,
+                        float *dgeo, float *s1, float *s0, float *workspace, float *dw0, int64_t ld_dw0, float *dw1, int64_t ld_dw1, float *dw2,
+                        int64_t ld_dw2, float *db2, void *stream, Launch launch) {
+    EMER_REQUIRE(n_rays >= 0 && kh >= 0, "%s: bad sizes", who);
+    if (n_rays == 0) return EMER_OK;
+    EMER_REQUIRE(emer_rgb_head_bwd_fused_supported(samples_per_ray), "%s: samples_per_ray must be a multiple of 16 (got %d)", who, samples_per_ray);
+    EMER_REQUIRE(own_ptrs && dout && out && geo && w0 && w1 && w2 && dgeo && s1 && s0 && workspace && dw0 && dw1 && dw2 && db2, "%s: null pointer", who);
+    EMER_REQUIRE(own_ld && ld_geo >= 64 && ld_geo % 4 == 0 && ld_dw0 >= 64 + kh && ld_dw1 >= 128 + kh && ld_dw2 >= 64, "%s: bad leading dimension", who);
+    EMER_REQUIRE(n_rays * samples_per_ray * ld_geo < ((int64_t)1 << 40), "%s: batch too large", who);
+    a.dout = dout; a.out = out; a.a1 = nullptr; a.a2 = nullptr; a.geo = geo; a.ld_geo = ld_geo; a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
+    const int64_t k0 = kh + 64, k1 = 64 + k0;
+    a.w2t = WSrc{w2, 1, 64, 64, 3};
+    a.w1at = WSrc{w1, 1, k1, 64, 64};
+    a.w1gt = WSrc{w1 + 64 + kh, 1, k1, 64, 64};
+    a.w0gt = WSrc{w0 + kh, 1, k0, 64, 64};
+    a.dgeo = dgeo; a.s1 = s1; a.s0 = s0; a.partials = workspace; a.stride = kRgbBwdWStride;
+    hipStream_t st = as_stream(stream);
+    const uint32_t grid = rgb_bwdw_grid(n_rays);
+    if (int rc = launch(grid, st)) return rc;
+    if (int rc = check_launch(who)) return rc;
+    // the workgroups' partials -> the parameters' gradients (+=): dW1's two column blocks land 0.. and 64 + kh.., dW0's at kh..
+    // (one launch for the three)
+    const DwReduceJob jb[3] = {{0, 64, 128, dw1, ld_dw1, nullptr, 2, {0, 64}, {64, 64}, {0, 64 + kh}},
+                               {64 * 128, 64, 64, dw0, ld_dw0, nullptr, 1, {0}, {64}, {kh}},
+                               {64 * 128 + 64 * 64, 3, 64, dw2, ld_dw2, db2, 0, {0}, {0}, {0}}};
+    return launch_dw_reduce_multi(workspace, (int32_t)grid, kRgbBwdWStride, 3, jb, st);
+}
+
 // Backward of emer_rgb_head_fwd INCLUDING the weight gradients of the per-sample column blocks: writes dgeo [n][64] and the per-ray
 // sums s1 / s0 [rays][64] of dpre1 / dpre0 (what the per-ray operands need: emer_ray_wgrad, emer_ray_pre_bwd); ACCUMULATES (+=)
 //   dw1[:, 0:64] += dpre1^T a1,  dw1[:, 64 + kh : 128 + kh] += dpre1^T geo   (dw1 [64][ld_dw1 >= 128 + kh], torch layout of layers.1.weight),
@@ -2796,33 +2726,15 @@ extern "C" int emer_rgb_head_bwd_fused(const float *dout, const float *out, cons
                                        int64_t n_rays, int32_t samples_per_ray, int32_t kh, const float *w0, const float *w1, const float *w2,
                                        float *dgeo, float *s1, float *s0, float *workspace, float *dw0, int64_t ld_dw0, float *dw1,
                                        int64_t ld_dw1, float *dw2, int64_t ld_dw2, float *db2, void *stream) {
-    EMER_REQUIRE(n_rays >= 0 && kh >= 0, "rgb_head_bwd_fused: bad sizes");
-    if (n_rays == 0) return EMER_OK;
-    EMER_REQUIRE(emer_rgb_head_bwd_fused_supported(samples_per_ray), "rgb_head_bwd_fused: samples_per_ray must be a multiple of 16 (got %d)", samples_per_ray);
-    EMER_REQUIRE(dout && out && a1 && a2 && geo && w0 && w1 && w2 && dgeo && s1 && s0 && workspace && dw0 && dw1 && dw2 && db2,
-                 "rgb_head_bwd_fused: null pointer");
-    EMER_REQUIRE(ld_geo >= 64 && ld_geo % 4 == 0 && ld_dw0 >= 64 + kh && ld_dw1 >= 128 + kh && ld_dw2 >= 64, "rgb_head_bwd_fused: bad leading dimension");
-    EMER_REQUIRE(n_rays * samples_per_ray * ld_geo < ((int64_t)1 << 40), "rgb_head_bwd_fused: batch too large");
     RgbBwdWArgs a;
-    a.dout = dout; a.out = out; a.a1 = a1; a.a2 = a2; a.geo = geo; a.ld_geo = ld_geo; a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
-    const int64_t k0 = kh + 64, k1 = 64 + k0;
-    a.w2t = WSrc{w2, 1, 64, 64, 3};
-    a.w1at = WSrc{w1, 1, k1, 64, 64};
-    a.w1gt = WSrc{w1 + 64 + kh, 1, k1, 64, 64};
-    a.w0gt = WSrc{w0 + kh, 1, k0, 64, 64};
-    a.dgeo = dgeo; a.s1 = s1; a.s0 = s0; a.partials = workspace; a.stride = kRgbBwdWStride;
-    const size_t lds = (size_t)(3 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * (2048 + 3072) * sizeof(float);
-    hipStream_t st = as_stream(stream);
-    const uint32_t grid = rgb_bwdw_grid(n_rays);
-    if (int rc = set_lds(rgb_bwdw16_kernel, lds, "rgb_head_bwd_fused")) return rc;
-    hipLaunchKernelGGL(rgb_bwdw16_kernel, dim3(grid), dim3(kRWThreads), lds, st, a);
-    if (int rc = check_launch("rgb_head_bwd_fused")) return rc;
-    // the workgroups' partials -> the parameters' gradients (+=): dW1's two column blocks land 0.. and 64 + kh.., dW0's at kh..
-    // (one launch for the three)
-    const DwReduceJob jb[3] = {{0, 64, 128, dw1, ld_dw1, nullptr, 2, {0, 64}, {64, 64}, {0, 64 + kh}},
-                               {64 * 128, 64, 64, dw0, ld_dw0, nullptr, 1, {0}, {64}, {kh}},
-                               {64 * 128 + 64 * 64, 3, 64, dw2, ld_dw2, db2, 0, {0}, {0}, {0}}};
-    return launch_dw_reduce_multi(workspace, (int32_t)grid, kRgbBwdWStride, 3, jb, st);
+    return rgb_bwdw_run("rgb_head_bwd_fused", a, a1 && a2, true, dout, out, geo, ld_geo, n_rays, samples_per_ray, kh, w0, w1, w2, dgeo, s1, s0,
+                        workspace, dw0, ld_dw0, dw1, ld_dw1, dw2, ld_dw2, db2, stream, [&](uint32_t grid, hipStream_t st) -> int {
+        a.a1 = a1; a.a2 = a2;
+        const size_t lds = (size_t)(3 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * (2048 + 3072) * sizeof(float);
+        if (int rc = set_lds(rgb_bwdw16_kernel, lds, "rgb_head_bwd_fused")) return rc;
+        hipLaunchKernelGGL(rgb_bwdw16_kernel, dim3(grid), dim3(kRWThreads), lds, st, a);
+        return EMER_OK;
+    });
 }
 
 // [r6] emer_rgb_head_bwd_fused WITHOUT saved activations: a1 / a2 are recomputed from geo and the per-ray pre-activations rb0 / rb1
@@ -2833,41 +2745,24 @@ extern "C" int emer_rgb_head_bwd_recompute(const float *dout, const float *out, 
                                            const float *w0, const float *w1, const float *w2, float *dgeo, float *s1, float *s0,
                                            float *workspace, float *dw0, int64_t ld_dw0, float *dw1, int64_t ld_dw1, float *dw2,
                                            int64_t ld_dw2, float *db2, void *stream) {
-    EMER_REQUIRE(n_rays >= 0 && kh >= 0, "rgb_head_bwd_recompute: bad sizes");
-    if (n_rays == 0) return EMER_OK;
-    EMER_REQUIRE(emer_rgb_head_bwd_fused_supported(samples_per_ray), "rgb_head_bwd_recompute: samples_per_ray must be a multiple of 16 (got %d)", samples_per_ray);
-    EMER_REQUIRE(dout && out && geo && rb0 && rb1 && w0 && w1 && w2 && dgeo && s1 && s0 && workspace && dw0 && dw1 && dw2 && db2,
-                 "rgb_head_bwd_recompute: null pointer");
-    EMER_REQUIRE(ld_geo >= 64 && ld_geo % 4 == 0 && ld_rb >= 64 && ld_dw0 >= 64 + kh && ld_dw1 >= 128 + kh && ld_dw2 >= 64,
-                 "rgb_head_bwd_recompute: bad leading dimension");
-    EMER_REQUIRE(n_rays * samples_per_ray * ld_geo < ((int64_t)1 << 40), "rgb_head_bwd_recompute: batch too large");
     RgbBwdRArgs a;
-    a.dout = dout; a.out = out; a.a1 = a1; a.geo = geo; a.ld_geo = ld_geo; a.rb0 = rb0; a.rb1 = rb1; a.ld_rb = ld_rb;
-    a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
-    const int64_t k0 = kh + 64, k1 = 64 + k0;
-    a.w0g = WSrc{w0 + kh, k0, 1, 64, 64};
-    a.w1a = WSrc{w1, k1, 1, 64, 64};
-    a.w1g = WSrc{w1 + 64 + kh, k1, 1, 64, 64};
-    a.w2t = WSrc{w2, 1, 64, 64, 3};
-    a.w1at = WSrc{w1, 1, k1, 64, 64};
-    a.w1gt = WSrc{w1 + 64 + kh, 1, k1, 64, 64};
-    a.w0gt = WSrc{w0 + kh, 1, k0, 64, 64};
-    a.dgeo = dgeo; a.s1 = s1; a.s0 = s0; a.partials = workspace; a.stride = kRgbBwdWStride;
-    const size_t lds = (size_t)(6 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * 256 * sizeof(float);
-    hipStream_t st = as_stream(stream);
-    const uint32_t grid = rgb_bwdw_grid(n_rays);
-    if (a1) {   // the cheaper half: a1 stored by the forward, a2 recomputed
-        if (int rc = set_lds(rgb_bwdwr_kernel<true>, lds, "rgb_head_bwd_recompute")) return rc;
-        hipLaunchKernelGGL(rgb_bwdwr_kernel<true>, dim3(grid), dim3(kRWThreads), lds, st, a);
-    } else {
-        if (int rc = set_lds(rgb_bwdwr_kernel<false>, lds, "rgb_head_bwd_recompute")) return rc;
-        hipLaunchKernelGGL(rgb_bwdwr_kernel<false>, dim3(grid), dim3(kRWThreads), lds, st, a);
-    }
-    if (int rc = check_launch("rgb_head_bwd_recompute")) return rc;
-    const DwReduceJob jb[3] = {{0, 64, 128, dw1, ld_dw1, nullptr, 2, {0, 64}, {64, 64}, {0, 64 + kh}},
-                               {64 * 128, 64, 64, dw0, ld_dw0, nullptr, 1, {0}, {64}, {kh}},
-                               {64 * 128 + 64 * 64, 3, 64, dw2, ld_dw2, db2, 0, {0}, {0}, {0}}};
-    return launch_dw_reduce_multi(workspace, (int32_t)grid, kRgbBwdWStride, 3, jb, st);
+    return rgb_bwdw_run("rgb_head_bwd_recompute", a, rb0 && rb1, ld_rb >= 64, dout, out, geo, ld_geo, n_rays, samples_per_ray, kh, w0, w1, w2, dgeo,
+                        s1, s0, workspace, dw0, ld_dw0, dw1, ld_dw1, dw2, ld_dw2, db2, stream, [&](uint32_t grid, hipStream_t st) -> int {
+        a.a1 = a1; a.rb0 = rb0; a.rb1 = rb1; a.ld_rb = ld_rb;
+        const int64_t k0 = kh + 64, k1 = 64 + k0;
+        a.w0g = WSrc{w0 + kh, k0, 1, 64, 64};
+        a.w1a = WSrc{w1, k1, 1, 64, 64};
+        a.w1g = WSrc{w1 + 64 + kh, k1, 1, 64, 64};
+        const size_t lds = (size_t)(6 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * 256 * sizeof(float);
+        if (a1) {   // the cheaper half: a1 stored by the forward, a2 recomputed
+            if (int rc = set_lds(rgb_bwdwr_kernel<true>, lds, "rgb_head_bwd_recompute")) return rc;
+            hipLaunchKernelGGL(rgb_bwdwr_kernel<true>, dim3(grid), dim3(kRWThreads), lds, st, a);
+        } else {
+            if (int rc = set_lds(rgb_bwdwr_kernel<false>, lds, "rgb_head_bwd_recompute")) return rc;
+            hipLaunchKernelGGL(rgb_bwdwr_kernel<false>, dim3(grid), dim3(kRWThreads), lds, st, a);
+        }
+        return EMER_OK;
+    });
 }
 
 // floats of workspace emer_rgb_head_bwd needs when it also produces dw2 / db2

@@ -50,6 +50,17 @@ template <> __device__ __forceinline__ void load_feats<8, __half>(const __half *
     v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
 }
 
+// one F-wide fp32 vector store where F has a vector type (float2 / float4)
+template <int F>
+__device__ __forceinline__ void store_feats(float *p, const float (&v)[F]) {
+    if (F == 2) { *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1 < F ? 1 : 0]); }
+    else if (F == 4) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1 < F ? 1 : 0], v[2 < F ? 2 : 0], v[3 < F ? 3 : 0]); }
+    else {
+#pragma unroll
+        for (int f = 0; f < F; ++f) p[f] = v[f];
+    }
+}
+
 template <int F>
 __device__ __forceinline__ void atomic_add_feats(float *p, const float (&v)[F]) {
 #pragma unroll
@@ -124,6 +135,13 @@ static LevelMap make_level_map(const emer_grid_desc *g, uint32_t n_chunks, uint3
     return lm;
 }
 
+// idx % size without the integer divide on the common paths (size is level-uniform)
+__device__ __forceinline__ uint32_t wrap_index(uint32_t idx, uint32_t size) {
+    if ((size & (size - 1u)) == 0u) return idx & (size - 1u);
+    if (idx >= size) { idx -= size; if (idx >= size) idx %= size; }
+    return idx;
+}
+
 template <int D>
 __device__ __forceinline__ uint32_t grid_index(const LevelInfo &li, const uint32_t (&c)[D]) {
     uint32_t idx;
@@ -140,10 +158,7 @@ __device__ __forceinline__ uint32_t grid_index(const LevelInfo &li, const uint32
             if (stride <= li.size) { idx += c[d] * stride; stride *= li.res; }
         }
     }
-    // idx % size without the integer divide on the common paths (size is level-uniform)
-    if ((li.size & (li.size - 1u)) == 0u) return idx & (li.size - 1u);
-    if (idx >= li.size) { idx -= li.size; if (idx >= li.size) idx %= li.size; }
-    return idx;
+    return wrap_index(idx, li.size);
 }
 
 template <int D>
@@ -169,6 +184,21 @@ __device__ __forceinline__ void cell_of(const LevelInfo &li, const float (&xv)[D
         gi[d] = (uint32_t)(int32_t)fl;
         w[d] = pos - fl;
     }
+}
+
+// Corner m of a cell (bit d of m: the upper neighbour along dimension d): its coordinates, and its interpolation weight
+// ((t0 * t1) * t2) * t3 with t_d = w[d] on the upper side and 1 - w[d] on the lower -- the oracle's product order.
+template <int D>
+__device__ __forceinline__ void corner_coords(const uint32_t (&gi)[D], uint32_t m, uint32_t (&c)[D]) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) c[d] = gi[d] + ((m >> d) & 1u);
+}
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&w)[D], uint32_t m) {
+    float wt = 1.0f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) wt *= (m & (1u << d)) ? w[d] : 1.0f - w[d];
+    return wt;
 }
 
 // slice plan of the owner-computes backward (described further down); the forward kernel emits the masks
@@ -425,8 +455,10 @@ __device__ __forceinline__ void set_row(uint64_t (&mask)[Q], uint32_t row) {
 // ------------------------------------------------------------------------------------ forward
 // JAC [r4]: rows n >= jac_row0 also store J[f][d] = d out[n][level][f] / d x[n][d] (jac[level][n - jac_row0][F][D]) -- the corner
 // values are in registers here anyway, and the input gradient of the flow configs becomes a streaming contraction of J with dOut
-// (hashgrid_bwd_input_jac_kernel) instead of a second pass of 2^D * L gathers per sample (hashgrid_bwd_input_kernel).  The encoding
-// itself is computed exactly as without JAC (same loop, same order).
+// (hashgrid_bwd_input_jac_kernel) instead of a second pass of 2^D * L gathers per sample (hashgrid_bwd_input_kernel).  JAC always takes
+// the generic corner loop.  Its encoding is therefore bitwise the plain forward's for entries larger than 16 bytes, and agrees to rounding
+// (atol 1e-6) for entries of 16 bytes or less, where the plain forward takes the pair path on hashed power-of-two levels: the same products
+// in the same order, contracted into multiply-adds differently (test_hashgrid_input_gradient_from_stored_jacobians asserts both).
 template <int D, int F, typename PT, int Q, bool JAC = false>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc g, const float *__restrict__ x,
                                                            const PT *__restrict__ params, float *__restrict__ out,
@@ -476,7 +508,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
             const bool x_pair_one_slice = li.res < (1u << plan.shift[level]) && !__ballot(gi[0] >= li.res);
 #pragma unroll
             for (uint32_t m = 0; m < (1u << (D - 1)); ++m) {
-                uint32_t h = 0;
+                uint32_t h = 0;  // (the pair term -- h and, below, wa / wb -- has twins in add_pair and add_pair_runs)
                 float t[D];
 #pragma unroll
                 for (int d = 1; d < D; ++d) {
@@ -512,13 +544,11 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
         if (!paired) {
 #pragma unroll
         for (uint32_t m = 0; m < (1u << D); ++m) {
-            float wt = 1.0f;
             uint32_t c[D];
+            corner_coords<D>(gi, m, c);
+            float wt = 1.0f;  // (twin of corner_weight, kept inline: through the helper the JAC instantiations need 1 to 6 registers more)
 #pragma unroll
-            for (int d = 0; d < D; ++d) {
-                if (m & (1u << d)) { wt *= w[d]; c[d] = gi[d] + 1u; }
-                else { wt *= 1.0f - w[d]; c[d] = gi[d]; }
-            }
+            for (int d = 0; d < D; ++d) wt *= (m & (1u << d)) ? w[d] : 1.0f - w[d];
             float v[F];
             const uint32_t idx = grid_index<D>(li, c);
             load_feats<F, PT>(table + (size_t)idx * F, v);
@@ -531,22 +561,14 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
             if (masks) set_row<Q>(mask, slice_of(plan, level, idx));  // by-product for the owner-computes backward
         }
         }
+        store_feats<F>(out + n * sn + (int64_t)level * sl, acc);
         if constexpr (JAC) {
-            // [r6] The encoding leaves FIRST.  hipcc used to schedule the Jacobian (and its four 16-byte stores) ahead of the accumulation
+            // [r6] The encoding has left FIRST.  hipcc used to schedule the Jacobian (and its four 16-byte stores) ahead of the accumulation
             // of the encoding; on gfx950 stores count in vmcnt like loads, so the waits that hand the gathered corners to the accumulation
             // (vmcnt 15 .. 0 in its model) then also waited for the Jacobian stores' acknowledgements -- a memory round trip in the
             // middle of every wave.  The barrier pins: accumulate, store the encoding, then the Jacobian (same-session A/B,
             // profiles/r06_xyzt_jac.txt: 448 -> 440 us at the 2048-ray shard, 1822 -> 1757 us at 8192 rays; results bitwise unchanged).
-            {
-                float *o = out + n * sn + (int64_t)level * sl;
-                if (F == 2) { *reinterpret_cast<float2 *>(o) = make_float2(acc[0], acc[1 < F ? 1 : 0]); }
-                else if (F == 4) { *reinterpret_cast<float4 *>(o) = make_float4(acc[0], acc[1 < F ? 1 : 0], acc[2 < F ? 2 : 0], acc[3 < F ? 3 : 0]); }
-                else {
-#pragma unroll
-                    for (int f = 0; f < F; ++f) o[f] = acc[f];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            __builtin_amdgcn_sched_barrier(0);
             if (n >= jac_row0) {
                 // J[f][gd] = scale * sum over the corners m with bit gd clear of prod_{d != gd} t_d(m) * (v[m | gd] - v[m])[f]:
                 // the same differences, weights and corner order as hashgrid_bwd_input_kernel forms after projecting on dOut
@@ -559,7 +581,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
 #pragma unroll
                     for (uint32_t m = 0; m < (1u << D); ++m) {
                         if (m & (1u << gd)) continue;
-                        float wt = li.scale;
+                        float wt = li.scale;  // (the derivative weight: twin of hashgrid_bwd_input_kernel's)
 #pragma unroll
                         for (int d = 0; d < D; ++d) {
                             if (d == gd) continue;
@@ -581,15 +603,6 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
                     for (int i = 0; i < F * D; ++i) jp[i] = J[i / D][i % D];
                 }
             }
-        }
-        if constexpr (!JAC) {
-        float *o = out + n * sn + (int64_t)level * sl;
-        if (F == 2) { *reinterpret_cast<float2 *>(o) = make_float2(acc[0], acc[1 < F ? 1 : 0]); }
-        else if (F == 4) { *reinterpret_cast<float4 *>(o) = make_float4(acc[0], acc[1 < F ? 1 : 0], acc[2 < F ? 2 : 0], acc[3 < F ? 3 : 0]); }
-        else {
-#pragma unroll
-            for (int f = 0; f < F; ++f) o[f] = acc[f];
-        }
         }
     }
     if (masks)  // the whole workgroup takes part (tail lanes carry an empty mask)
@@ -621,6 +634,8 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_params_kernel(const emer_gri
     cell_of<D>(li, xv, gi, w);
 #pragma unroll
     for (uint32_t m = 0; m < (1u << D); ++m) {
+        // (twin of corner_coords / corner_weight, kept inline: with the helpers the one-feature D = 3 instantiation measured 0.2 % over
+        // the parent where its spread was 0.15 %, profiles/grid_dedup_ab.json)
         float wt = 1.0f;
         uint32_t c[D];
 #pragma unroll
@@ -832,6 +847,7 @@ __device__ __forceinline__ void add_pair(double *acc, const uint32_t (&gi)[D], c
     const bool has = match != 0u;
     const uint32_t m = has ? (uint32_t)__ffs((int)match) - 1u : 0u;
     match &= match - 1u;  // (0 stays 0)
+    // (the pair term h, wa, wb: twin of add_pair_runs' and of the forward's paired branch -- one helper for them costs registers or scratch)
     uint32_t h = 0;
     float wa = 1.0f - w[0], wb = w[0];  // same product order as the generic path: ((t0*t1)*t2)*t3
 #pragma unroll
@@ -880,7 +896,8 @@ __device__ __forceinline__ void add_pair(double *acc, const uint32_t (&gi)[D], c
 template <int D, int F>
 __device__ __forceinline__ void add_pair_runs(double *acc, const uint32_t (&gi)[D], const float (&w)[D], const uint32_t (&hd)[D][2],
                                               const float (&go)[F], uint32_t &match, uint32_t local_mask, bool valid, int lane) {
-    // run heads: a lane whose cell differs from its predecessor's (invalid lanes are runs of their own)
+    // run heads: a lane whose cell differs from its predecessor's (invalid lanes are runs of their own); head / RunMasks / next_head
+    // have a twin in the dense path of the sliced kernel
     uint32_t diff = 0;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -893,7 +910,7 @@ __device__ __forceinline__ void add_pair_runs(double *acc, const uint32_t (&gi)[
     const bool has = match != 0u;
     const uint32_t m = has ? (uint32_t)__ffs((int)match) - 1u : 0u;
     match &= match - 1u;
-    uint32_t h = 0;
+    uint32_t h = 0;  // (the pair term: twin of add_pair's)
     float wa = 1.0f - w[0], wb = w[0];
 #pragma unroll
     for (int d = 1; d < D; ++d) {
@@ -919,9 +936,7 @@ __device__ __forceinline__ void add_pair_runs(double *acc, const uint32_t (&gi)[
 // queued pairs.
 template <int D, int F>
 __device__ __forceinline__ void drain_pair_queue(double *acc, const LevelInfo &li, const float *__restrict__ x, const float *__restrict__ dl,
-                                                 int64_t sn, const uint32_t *Qw, uint32_t q_head, uint32_t count, uint32_t slice_want,
-                                                 uint32_t slice_bits, uint32_t local_mask, int lane) {
-    (void)slice_want; (void)slice_bits;
+                                                 int64_t sn, const uint32_t *Qw, uint32_t q_head, uint32_t count, uint32_t local_mask, int lane) {
     const bool on = (uint32_t)lane < count;
     const uint32_t e = on ? Qw[(q_head + (uint32_t)lane) % kPairQueue] : 0u;
     uint32_t n = e >> 8;
@@ -1022,7 +1037,7 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
     // are pairable too -- the x-neighbours still share a slice unless x sits at the last position of a slice-wide block, a 1-in-4096
     // event handled like the out-of-range wrap (wave-uniform fallback to the per-corner path).  Before, those levels took the per-corner
     // path for EVERY hit: 680 us per work item against 450 us for the level below them (tools/trace_sliced.py).
-    const bool pairable_rt = li.hashed && (li.size & (li.size - 1u)) == 0u && true;
+    const bool pairable_rt = li.hashed && (li.size & (li.size - 1u)) == 0u;
     const bool run_reduced = pairable_rt && F >= 2 && li.res <= (uint32_t)EMER_RUN_RES;  // coarse hashed level: runs of equal cells are summed before the LDS
     const bool consecutive = dense_rt || run_reduced || li.res > kStridedHitsMaxRes;  // hit -> lane assignment, see the compaction below
     const uint32_t shift = plan.shift[level], n_ranges = plan.n_ranges[level];
@@ -1187,15 +1202,17 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
             const float *xp = reinterpret_cast<const float *>(reinterpret_cast<const char *>(x) + xoff);
             const float *gp = reinterpret_cast<const float *>(reinterpret_cast<const char *>(dl) + (uint32_t)(n * (uint32_t)(F * 4)));
             load_x<D>(xp, 0, G.xs[k]);
-            if (F == 2) { float2 t = *reinterpret_cast<const float2 *>(gp); G.go[k][0] = t.x; G.go[k][1 < F ? 1 : 0] = t.y; }
-            else if (F == 4) { float4 t = *reinterpret_cast<const float4 *>(gp); G.go[k][0] = t.x; G.go[k][1 < F ? 1 : 0] = t.y; G.go[k][2 < F ? 2 : 0] = t.z; G.go[k][3 < F ? 3 : 0] = t.w; }
-            else {
-#pragma unroll
-                for (int f = 0; f < F; ++f) G.go[k][f] = gp[f];
-            }
+            load_feats<F, float>(gp, G.go[k]);
         }
         c0 += (uint32_t)KG;
         return have;
+    };
+    // up to 64 queued second pairs leave the ring, one per lane
+    auto drain_queue = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const uint32_t done = q_len < 64u ? q_len : 64u;
+        drain_pair_queue<D, F>(acc, li, x, dl, sn, Qw, q_head, done, local_mask, lane);
+        q_head = (q_head + done) % kPairQueue; q_len -= done;
     };
     auto consume = [&](HitGroup<D, F, KG> &G) __attribute__((always_inline)) {
 #pragma unroll
@@ -1215,6 +1232,7 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
 #pragma unroll
                 for (int d = 0; d < D; ++d) { cell += gi[d] * mul; mul *= li.res + 1u; }
                 if (!valid) cell = 0xFFFFFFFFu;
+                // (head / RunMasks / next_head: twin of add_pair_runs')
                 const uint32_t prev = wave_prev_u32(cell, ~cell);
                 const bool head = cell != prev;  // (lane 0 compares with ~cell: always a head)
                 const RunMasks rm = run_masks(head);
@@ -1234,20 +1252,16 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
                 }
 #pragma unroll
                 for (uint32_t m = 0; m < (1u << D); ++m) {
-                    float wt = 1.0f;
+                    const float wt = corner_weight<D>(w, m);
                     uint32_t off_m = 0;
 #pragma unroll
-                    for (int d = 0; d < D; ++d) {
+                    for (int d = 0; d < D; ++d)
                         if (m & (1u << d)) off_m += stride_d[d];
-                        wt *= (m & (1u << d)) ? w[d] : 1.0f - w[d];
-                    }
                     float v[F];
 #pragma unroll
                     for (int f = 0; f < F; ++f) v[f] = wt * G.go[k][f];
                     run_reduce_dpp<F>(v, rm);
-                    uint32_t idx = cell_idx + off_m;
-                    if ((li.size & (li.size - 1u)) == 0u) idx &= li.size - 1u;
-                    else if (idx >= li.size) { idx -= li.size; if (idx >= li.size) idx %= li.size; }
+                    const uint32_t idx = wrap_index(cell_idx + off_m, li.size);
                     if (tail && (idx >> shift) == slice) {
 #pragma unroll
                         for (int f = 0; f < F; ++f) atomicAdd(acc + (size_t)(idx - first) * F + f, (double)v[f]);
@@ -1292,12 +1306,8 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
 #pragma unroll
                 for (uint32_t m = 0; m < (1u << D); ++m) {
                     uint32_t c[D];
-                    float wt = 1.0f;
-#pragma unroll
-                    for (int d = 0; d < D; ++d) {
-                        c[d] = gi[d] + ((m >> d) & 1u);
-                        wt *= (m & (1u << d)) ? w[d] : 1.0f - w[d];
-                    }
+                    corner_coords<D>(gi, m, c);
+                    const float wt = corner_weight<D>(w, m);
                     const uint32_t idx = grid_index<D>(li, c);
                     if (valid && (idx >> shift) == slice) {
 #pragma unroll
@@ -1309,12 +1319,7 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
         if constexpr (pairable) {
             // queued second pairs are drained BETWEEN groups (its gathers would otherwise sit inside the chunk loop and make
             // the wait counts of the pipelined gathers conservative: vmcnt(0) after every chunk)
-            if (q_len >= kPairQueueDrain) {  // wave-uniform
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                const uint32_t done = q_len < 64u ? q_len : 64u;
-                drain_pair_queue<D, F>(acc, li, x, dl, sn, Qw, q_head, done, slice_want, slice_bits, local_mask, lane);
-                q_head = (q_head + done) % kPairQueue; q_len -= done;
-            }
+            if (q_len >= kPairQueueDrain) drain_queue();  // wave-uniform
         }
     };
     {
@@ -1329,12 +1334,7 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
             consume(gb);
         }
     }
-    while (q_len) {  // wave-uniform: second pairs still queued
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint32_t done = q_len < 64u ? q_len : 64u;
-        drain_pair_queue<D, F>(acc, li, x, dl, sn, Qw, q_head, done, slice_want, slice_bits, local_mask, lane);
-        q_head = (q_head + done) % kPairQueue; q_len -= done;
-    }
+    while (q_len) drain_queue();  // wave-uniform: second pairs still queued
     };  // run_item
     if (dense_rt) run_item(std::integral_constant<int, 0>{});
     else if (pairable_rt) run_item(std::integral_constant<int, 1>{});
@@ -1397,8 +1397,7 @@ __global__ __launch_bounds__(256) void hashgrid_slice_masks_kernel(const emer_gr
 #pragma unroll
         for (uint32_t m = 0; m < (1u << D); ++m) {
             uint32_t c[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) c[d] = gi[d] + ((m >> d) & 1u);
+            corner_coords<D>(gi, m, c);
             set_row<Q>(mask, slice_of(plan, level, grid_index<D>(li, c)));
         }
     }
@@ -1432,8 +1431,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_input_kernel(const emer_grid
 #pragma unroll
         for (uint32_t m = 0; m < (1u << D); ++m) {
             uint32_t c[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) c[d] = gi[d] + ((m >> d) & 1u);
+            corner_coords<D>(gi, m, c);
             float v[F];
             load_feats<F, PT>(table + (size_t)grid_index<D>(li, c) * F, v);
             float a = 0.0f;
@@ -1447,7 +1445,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_input_kernel(const emer_grid
 #pragma unroll
             for (uint32_t m = 0; m < (1u << D); ++m) {
                 if (m & (1u << gd)) continue;  // enumerate corners with bit gd == 0
-                float wt = li.scale;
+                float wt = li.scale;  // (the derivative weight: twin of the Jacobian forward's)
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
                     if (d == gd) continue;
@@ -1519,6 +1517,40 @@ static int check_desc(const emer_grid_desc *g) {
     return EMER_OK;
 }
 
+// What the entry points that walk the (level, chunk) blocks prepare: the block map and, for the kernels that take it, the slice plan.
+struct GridLaunch {
+    uint32_t n_chunks, blocks;
+    LevelMap lmap;
+    SlicePlan plan;   // (set by prepare_grid_launch_with_plan only)
+};
+static void prepare_grid_launch(const emer_grid_desc *g, int64_t n, GridLaunch &gl) {
+    gl.n_chunks = (uint32_t)ceil_div(n, 256);
+    gl.lmap = make_level_map(g, gl.n_chunks, &gl.blocks);
+}
+// `plan_error`: the launch writes slice bitmaps, so the plan must hold (the text to fail with); null when it writes none.
+static int prepare_grid_launch_with_plan(const emer_grid_desc *g, int64_t n, const char *plan_error, GridLaunch &gl) {
+    prepare_grid_launch(g, n, gl);
+    gl.plan = make_slice_plan(g);
+    EMER_REQUIRE(!plan_error || gl.plan.ok, "%s", plan_error);
+    return EMER_OK;
+}
+// Q of the kernels that write slice bitmaps (64-row groups of bitmap rows per level): the plan's when bitmaps are written, else 1
+template <typename Fn>
+static void dispatch_q(bool write_masks, const SlicePlan &plan, Fn &&fn) {
+    if (write_masks && plan.mask_q == 4) fn(std::integral_constant<int, 4>{});  // 256 bitmap rows per level
+    else fn(std::integral_constant<int, 1>{});
+}
+// the one launch of hashgrid_fwd_kernel
+template <int D, int F, typename PT, bool JAC>
+static void launch_fwd(const GridLaunch &gl, const emer_grid_desc *g, const float *x, const PT *params, float *out, int64_t sn, int64_t sl,
+                       uint64_t *slice_masks, float *jac, int64_t jac_row0, int64_t n, void *stream) {
+    const ProfileEvents ev = take_profile_events();  // (null unless emer_profile_next armed them)
+    dispatch_q(slice_masks != nullptr, gl.plan, [&](auto q) {
+        EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, PT, decltype(q)::value, JAC>), dim3(gl.blocks), dim3(256), 0, as_stream(stream), *g, x,
+                             params, out, sn, sl, n, gl.n_chunks, gl.lmap, gl.plan, slice_masks, jac, jac_row0);
+    });
+}
+
 }  // namespace emer
 
 using namespace emer;
@@ -1530,30 +1562,13 @@ extern "C" int emer_hashgrid_fwd(const emer_grid_desc *g, const float *x, const 
     if (n == 0) return EMER_OK;
     EMER_REQUIRE(x && params && out, "hashgrid_fwd: null pointer");
     EMER_REQUIRE(param_dtype == EMER_F32 || param_dtype == EMER_F16, "hashgrid_fwd: bad param_dtype %d", param_dtype);
-    const uint32_t n_chunks = (uint32_t)ceil_div(n, 256);
-    uint32_t blocks = 0;
-    const LevelMap lmap = make_level_map(g, n_chunks, &blocks);
-    const SlicePlan plan = make_slice_plan(g);
-    EMER_REQUIRE(!slice_masks || plan.ok, "hashgrid_fwd: slice bitmaps requested but a level needs more than 256 x 64 LDS slices");
-    const ProfileEvents ev = take_profile_events();  // (null unless emer_profile_next armed them)
+    GridLaunch gl;
+    if (int rc = prepare_grid_launch_with_plan(g, n, slice_masks ? "hashgrid_fwd: slice bitmaps requested but a level needs more than 256 x 64 LDS slices" : nullptr, gl))
+        return rc;
     return dispatch_df(g->n_dims, g->n_features, [&](auto d, auto f) {
         constexpr int D = decltype(d)::value, F = decltype(f)::value;
-        const bool wide = slice_masks && plan.mask_q == 4;  // 256 bitmap rows per level
-        if (param_dtype == EMER_F32) {
-            if (wide)
-                EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, float, 4>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x,
-                                     (const float *)params, out, sn, sl, n, n_chunks, lmap, plan, slice_masks, (float *)nullptr, (int64_t)0);
-            else
-                EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, float, 1>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x,
-                                     (const float *)params, out, sn, sl, n, n_chunks, lmap, plan, slice_masks, (float *)nullptr, (int64_t)0);
-        } else {
-            if (wide)
-                EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, __half, 4>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x,
-                                     (const __half *)params, out, sn, sl, n, n_chunks, lmap, plan, slice_masks, (float *)nullptr, (int64_t)0);
-            else
-                EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, __half, 1>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x,
-                                     (const __half *)params, out, sn, sl, n, n_chunks, lmap, plan, slice_masks, (float *)nullptr, (int64_t)0);
-        }
+        if (param_dtype == EMER_F32) launch_fwd<D, F, float, false>(gl, g, x, (const float *)params, out, sn, sl, slice_masks, nullptr, 0, n, stream);
+        else launch_fwd<D, F, __half, false>(gl, g, x, (const __half *)params, out, sn, sl, slice_masks, nullptr, 0, n, stream);
         return check_launch("hashgrid_fwd");
     });
 }
@@ -1567,20 +1582,11 @@ extern "C" int emer_hashgrid_fwd_jac(const emer_grid_desc *g, const float *x, co
     if (n == 0) return EMER_OK;
     EMER_REQUIRE(x && params && out && (jac || jac_row0 == n), "hashgrid_fwd_jac: null pointer");
     EMER_REQUIRE(((uintptr_t)jac % 16) == 0, "hashgrid_fwd_jac: jac must be 16-byte aligned");
-    const uint32_t n_chunks = (uint32_t)ceil_div(n, 256);
-    uint32_t blocks = 0;
-    const LevelMap lmap = make_level_map(g, n_chunks, &blocks);
-    const SlicePlan plan = make_slice_plan(g);
-    EMER_REQUIRE(!slice_masks || plan.ok, "hashgrid_fwd_jac: slice bitmaps requested but a level needs more than 256 x 64 LDS slices");
-    const ProfileEvents ev = take_profile_events();
+    GridLaunch gl;
+    if (int rc = prepare_grid_launch_with_plan(g, n, slice_masks ? "hashgrid_fwd_jac: slice bitmaps requested but a level needs more than 256 x 64 LDS slices" : nullptr, gl))
+        return rc;
     return dispatch_df(g->n_dims, g->n_features, [&](auto d, auto f) {
-        constexpr int D = decltype(d)::value, F = decltype(f)::value;
-        if (slice_masks && plan.mask_q == 4)
-            EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, float, 4, true>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x, params, out,
-                                 sn, sl, n, n_chunks, lmap, plan, slice_masks, jac, jac_row0);
-        else
-            EMER_LAUNCH_PROFILED(ev, (hashgrid_fwd_kernel<D, F, float, 1, true>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, x, params, out,
-                                 sn, sl, n, n_chunks, lmap, plan, slice_masks, jac, jac_row0);
+        launch_fwd<decltype(d)::value, decltype(f)::value, float, true>(gl, g, x, params, out, sn, sl, slice_masks, jac, jac_row0, n, stream);
         return check_launch("hashgrid_fwd_jac");
     });
 }
@@ -1610,18 +1616,17 @@ extern "C" int emer_hashgrid_bwd_params(const emer_grid_desc *g, const float *x,
     EMER_REQUIRE(x && dout && grad, "hashgrid_bwd_params: null pointer");
     EMER_REQUIRE(grad_dtype == EMER_F32 || grad_dtype == EMER_F16, "hashgrid_bwd_params: bad grad_dtype %d", grad_dtype);
     EMER_REQUIRE(!(grad_dtype == EMER_F16 && (g->n_features & 1u)), "hashgrid_bwd_params: fp16 gradients need an even n_features");
-    const uint32_t n_chunks = (uint32_t)ceil_div(n, 256);
-    uint32_t blocks = 0;
-    const LevelMap lmap = make_level_map(g, n_chunks, &blocks);
+    GridLaunch gl;
+    prepare_grid_launch(g, n, gl);
     return dispatch_df(g->n_dims, g->n_features, [&](auto d, auto f) {
         constexpr int D = decltype(d)::value, F = decltype(f)::value;
         if (grad_dtype == EMER_F32) {
-            hipLaunchKernelGGL((hashgrid_bwd_params_kernel<D, F, float>), dim3(blocks), dim3(256), 0, as_stream(stream), *g,
-                               x, dout, sn, sl, (float *)grad, n, n_chunks, lmap);
+            hipLaunchKernelGGL((hashgrid_bwd_params_kernel<D, F, float>), dim3(gl.blocks), dim3(256), 0, as_stream(stream), *g,
+                               x, dout, sn, sl, (float *)grad, n, gl.n_chunks, gl.lmap);
         } else {
             if constexpr (F % 2 == 0)
-                hipLaunchKernelGGL((hashgrid_bwd_params_kernel<D, F, __half>), dim3(blocks), dim3(256), 0, as_stream(stream),
-                                   *g, x, dout, sn, sl, (__half *)grad, n, n_chunks, lmap);
+                hipLaunchKernelGGL((hashgrid_bwd_params_kernel<D, F, __half>), dim3(gl.blocks), dim3(256), 0, as_stream(stream),
+                                   *g, x, dout, sn, sl, (__half *)grad, n, gl.n_chunks, gl.lmap);
         }
         return check_launch("hashgrid_bwd_params");
     });
@@ -1648,26 +1653,22 @@ extern "C" int emer_hashgrid_slice_masks(const emer_grid_desc *g, const float *x
     EMER_REQUIRE(n >= 0, "hashgrid_slice_masks: negative n");
     if (n == 0) return EMER_OK;
     EMER_REQUIRE(x && slice_masks, "hashgrid_slice_masks: null pointer");
-    const SlicePlan plan = make_slice_plan(g);
-    EMER_REQUIRE(plan.ok, "hashgrid_slice_masks: a level needs more than 256 x 64 LDS slices");
-    const uint32_t n_chunks = (uint32_t)ceil_div(n, 256);
-    uint32_t blocks = 0;
-    const LevelMap lmap = make_level_map(g, n_chunks, &blocks);
+    GridLaunch gl;
+    if (int rc = prepare_grid_launch_with_plan(g, n, "hashgrid_slice_masks: a level needs more than 256 x 64 LDS slices", gl)) return rc;
     return dispatch_df(g->n_dims, g->n_features, [&](auto d, auto) {
-        constexpr int D = decltype(d)::value;
-        if (plan.mask_q == 4)
-            hipLaunchKernelGGL((hashgrid_slice_masks_kernel<D, 4>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, plan, x, slice_masks, n,
-                               n_chunks, lmap);
-        else
-            hipLaunchKernelGGL((hashgrid_slice_masks_kernel<D, 1>), dim3(blocks), dim3(256), 0, as_stream(stream), *g, plan, x, slice_masks, n,
-                               n_chunks, lmap);
+        dispatch_q(true, gl.plan, [&](auto q) {
+            hipLaunchKernelGGL((hashgrid_slice_masks_kernel<decltype(d)::value, decltype(q)::value>), dim3(gl.blocks), dim3(256), 0, as_stream(stream),
+                               *g, gl.plan, x, slice_masks, n, gl.n_chunks, gl.lmap);
+        });
         return check_launch("hashgrid_slice_masks");
     });
 }
 
 // Owner-computes variant: OVERWRITES grad (f32) -- every entry of every level is written exactly
 // once, so the caller does not zero the buffer.  The slice bitmaps come from emer_hashgrid_fwd (or
-// emer_hashgrid_slice_masks) for the SAME x.
+// emer_hashgrid_slice_masks) for the SAME x.  dout is gathered with F-wide vector loads (load_feats): each level's rows
+// (dout + level * stride_l) must be aligned to min(F * 4, 16) bytes, which a packed level-major tensor from a 16-byte-aligned
+// allocation is.
 static int hashgrid_bwd_params_sliced_range(const emer_grid_desc *g, const float *x, const float *dout, int64_t sn, int64_t sl,
                                             uint64_t *slice_masks, float *grad, int64_t n, uint32_t level_begin, uint32_t level_end, void *stream,
                                             bool accumulate = false);

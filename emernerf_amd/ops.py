@@ -984,7 +984,12 @@ class _LidarLossFn(torch.autograd.Function):
 def lidar_loss(depth: Tensor, weights: Tensor, lidar_ranges: Tensor, t_vals: Tensor, epsilon: float, max_depth: float = 80.0,
                w_depth: float = 1.0, w_sight: float = 0.1) -> Tensor:
     """Depth (loss/base.py:188-271, l2) + line-of-sight (loss/base.py:430-464) supervision as one scalar; gradients flow
-    to the rendered depth [R,1] and the rendering weights [R,S]."""
+    to the rendered depth [R,1] and the rendering weights [R,S].
+
+    One divergence from the reference: a batch with NO valid ray (none with 0.01 < range < max_depth).  The reference's depth
+    term is the mean of an empty tensor there, NaN (loss/base.py:60-72, 240-248); here the depth term is 0, its gradient is
+    exact zeros and the valid count is never divided by, so the total stays finite and the line-of-sight term is unchanged.
+    A batch with no ray of range > 0 has a line-of-sight term and weight gradients of exactly 0, as in the reference."""
     _check_cuda(depth, weights, lidar_ranges, t_vals)
     return _LidarLossFn.apply(depth, weights, lidar_ranges, t_vals, epsilon, max_depth, w_depth, w_sight)
 

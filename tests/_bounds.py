@@ -585,3 +585,112 @@ def assert_err_bound(got, ref, err, what: str, report: dict = None) -> float:
     ref = np.asarray(ref, np.float64)
     return assert_bound(np.asarray(got, np.float64).reshape(ref.shape), ref, np.broadcast_to(np.asarray(err, np.float64), ref.shape) / U, 1.0,
                         what, report=report)
+
+
+# ------------------------------------------------------------------------------------------------------ loss kernels
+# pixel_loss, lidar_loss and reg_losses of csrc/rayloss.hip on arbitrary fp32 inputs (tests/_loss_probe.py has the fp64
+# restatements whose values these take).  First order, one rounding (relative u) per fp32 operation, a host float that
+# arrives as a c_float counted as one; a contracted multiply-add only removes roundings.
+#
+# The one constant that is not derived is the device logf's error.  Measured on an MI355X through pixel_loss_fwd itself
+# (sky-only, w_sky = 1, R = 2^23, so that loss_rays[r] = -logf(arg_r) / R exactly) on the 8 388 608 opacities of
+# tests/test_loss_exact_gpu._logf_sweep(23) in [1e-6, 1]: 2^21 log-spaced from 1e-6, 2^21 of 1 - log-spaced down to 1 - 1e-7,
+# 2^20 each of uniform random, dense random in [1e-6, 1e-3], dense random in [0.999, 1] and a uniform grid; once with
+# sky_mask = 0 for logf(o) and once with sky_mask = 1 for logf(fl(1 - o)), against float64 log of the fp32 argument: at most
+# 2.140 ulp for logf(o) (at o = 1.4565692e-05) and 2.143 ulp for logf(1 - o) (at 1 - o = 0.061523914); 48 % of the results are
+# not the correctly rounded one; about 2.1 ulp throughout (0, 0.5] and 1.9 ulp in (0.5, 1); logf(1) = 0 and logf(0) = -inf
+# (clamped to -100) exactly.  E_LOGF is the measured maximum rounded up to the next integer plus one ulp of margin (the rule
+# E_EXPF follows); one ulp is at most 2 u relative.  test_device_logf_error_is_inside_E_LOGF runs _logf_sweep(20), the same
+# generator at 2^20 arguments, in the suite and fails if the device's logf ever leaves E_LOGF - 1.
+E_LOGF_MEASURED = 2.143  # ulps
+E_LOGF = 4.0
+
+C_PIX_RGB = 10.0   # w s / (3 R): d = fl(a - b) squared 3, the sum of three 2, the c_float w, the product, fl(3 R), the division 4; slack 1
+C_PIX_DRGB = 7.0   # up w 2 d / (3 R): the c_float w gs, up w, d, the product, fl(3 R), the division; slack 1
+C_PIX_DOPA = 9.0   # up w (o - t) / max(o fl(1 - o), 1e-12f) / R: w gs, up w, o - t, the product, 1 - o, o (1 - o), two divisions; slack 1
+
+
+def pixel_bounds(st: dict) -> dict:
+    """Per-ray pixel loss and its two gradients from ``restate_pixel``'s values.
+
+    * rgb term: C_PIX_RGB u |term|;
+    * BCE = -(t max(logf(o), -100) + (1 - t) max(logf(fl(1 - o)), -100)): logf carries 2 E_LOGF u |log|; fl(1 - o) carries a
+      relative u, which is an ABSOLUTE -log1p(-u) in its logarithm (near o = 1 the term log(1 - o) sees the absolute rounding of
+      1 - o); a clamped logarithm is exact; the two products and the sum: u (|A| + |B|) + u |A + B|; w bce / R: the c_float w, the
+      product and the division, 3 u;
+    * the sum of the two terms: u |ray|;  the gradients: C_PIX_DRGB / C_PIX_DOPA u |value| (the floor 1e-12f is the same constant
+      in the restatement, and o (1 - o) is never near it for o in [1e-6, 1] unless it is exactly 0)."""
+    a = np.abs
+    R = st["R"]
+    e_sky = np.zeros(R)
+    if "o" in st:
+        t = st["t"]
+        lo, l1 = np.maximum(st["log_o"], -100.0), np.maximum(st["log_1mo"], -100.0)
+        rel = 2 * E_LOGF * U
+        r1 = -np.log1p(-U)
+        e_lo = np.where(st["log_o"] > -100.0, rel * a(lo), 0.0)
+        e_l1 = np.where(st["log_1mo"] > -100.0, r1 + rel * (a(l1) + r1), 0.0)
+        e_bce = a(t) * e_lo + a(1 - t) * e_l1 + U * (a(st["A"]) + a(st["B"])) + U * a(st["A"] + st["B"])
+        e_sky = a(st["w_sky"]) / R * e_bce + 3 * U * a(st["sky_term"])
+    out = dict(rays=C_PIX_RGB * U * a(st["rgb_term"]) + e_sky + U * a(st["rays"]))
+    if st.get("d_rgb") is not None:
+        out["d_rgb"] = C_PIX_DRGB * U * a(st["d_rgb"])
+    if st.get("d_opa") is not None:
+        out["d_opa"] = C_PIX_DOPA * U * a(st["d_opa"])
+    return out
+
+
+C_LIDAR_SCALE = 4.0   # scale = w_sight fl(n_pos / R) / R: the c_float w_sight, two divisions, one product
+C_LIDAR_NORM = 6.0    # norm = 1 / sqrtf(2 pi_f sigma sigma), sigma = fl(fl(eps) / 3): pi_f 1, sigma 2 twice, two products 2 -> 7 u under
+#                       the root = 3.5 u, the root 1, the division 1: 5.5 u against 1 / sqrt(2 pi (eps / 3)^2) in double
+C_LIDAR_INV2S2 = 6.0  # inv2s2 = 1 / (2 sigma sigma): sigma 2 twice, one product, the division
+
+
+def lidar_bounds(st: dict, eps: float) -> dict:
+    """Per-ray lidar loss, d_depth and d_weights from ``restate_lidar``'s values.
+
+    * x = fl(t - gt): u |x|; the argument a = fl(fl(x x) inv2s2): (2 + 1 + C_LIDAR_INV2S2 + 1) u a -- an ABSOLUTE error of the
+      argument, which is a RELATIVE error expm1(e_a) of expf (a <= 4.5 in the band: inside the range E_EXPF was swept over);
+      delta = fl(norm expf(-a)): (expm1(e_a) + 2 E_EXPF u + (C_LIDAR_NORM + 1) u) delta;
+    * e = fl(w - delta): e_delta + u (|w| + |delta|) -- held to |w| + |delta|, not to |e|; term = e e: 2 |e| e_e + u e^2; an empty-band
+      term w w: u w^2; a sample in neither band: exactly 0;
+    * the wave sum: every term passes at most ceil(S / 64) + 6 additions: that many u on the abs-sum (the terms are non-negative);
+    * d_w = fl(fl(up scale) dw): |up scale| 2 e_e + (C_LIDAR_SCALE + 2) u |up scale| 2 (|w| + |delta|) (empty band: 2 |w|);
+    * depth: pn, gn one division each, d = fl(pc - gn): u (|pc| + |gn| + |d|); w_depth d d / n_valid: 2 |d| e_d w / n + 4 u |l|;
+      d_depth = up w 2 d / (max n): |.| e_d / |d| ... + 5 u |value|; exactly 0 on an invalid ray and where the clamp blocks;
+    * loss_rays = fl(l + fl(scale acc)): + (C_LIDAR_SCALE + 1) u on the sight share, + u |ray|."""
+    a = np.abs
+    S = st["S"]
+    w, delta, e, arg, x = st["w"], st["delta"], st["e"], st["arg"], st["x"]
+    near, empty = st["near"], st["empty"]
+    e_a = (4 + C_LIDAR_INV2S2) * U * arg
+    r_d = np.expm1(e_a)
+    e_delta = delta * (r_d + (2 * E_EXPF + C_LIDAR_NORM + 1) * U * (1 + r_d)) + TINY
+    e_e = e_delta + U * (a(w) + delta)
+    e_term = np.where(empty, U * w * w, np.where(near, 2 * a(e) * e_e + e_e ** 2 + U * e * e, 0.0))
+    dw_abs = np.where(empty, 2 * a(w), np.where(near, 2 * (a(w) + delta), 0.0))
+    k = abs(st["up"] * st["scale"])
+    e_dw = k * np.where(near, 2 * e_e, 0.0) + (C_LIDAR_SCALE + 2) * U * k * dw_abs
+    term = st["term"]
+    e_acc = e_term.sum(1) + (-(-S // 64) + 6) * U * term.sum(1)
+    sc = abs(st["scale"])
+    nv = max(st["n_valid"], 1)
+    d, wd, mx = st["d"], abs(st["w_depth"]), st["max_depth"]
+    e_d = U * (a(st["pc"]) + a(st["gn"]) + a(d))
+    e_ld = np.where(st["valid"], 2 * a(d) * e_d * wd / nv + 4 * U * a(st["ray_depth"]), 0.0)
+    e_dd = np.where(st["valid"] & st["passes"], abs(st["up"]) * wd * 2 * e_d / (mx * nv) + 5 * U * a(st["d_depth"]), 0.0)
+    e_rays = e_ld + sc * e_acc + (C_LIDAR_SCALE + 1) * U * sc * term.sum(1) + U * a(st["rays"])
+    return dict(rays=e_rays, d_depth=e_dd, d_w=e_dw)
+
+
+C_REG_GRAD_CONST = 5.0   # up gs (c / n): the c_float gs and c, up gs, c / n, the product; slack 0
+C_REG_GRAD = 8.0         # g (a - b) with g = up gs (2 c / n): 5 as above, the difference / sum of two fp32 inputs, the product; slack 1
+
+
+def reg_partial_bound(name: str, n: int, stride: int) -> float:
+    """Roundings a term of a reg_losses block partial passes, against (c / n) sum |term| over the block's elements: the
+    per-thread strided chain ceil(n / stride), the 6 steps of the wave butterfly, the 4 wave partials, the c_float c, c / n and
+    the product 3, the `l +=` of up to four terms 3, and the term's own: 0 (dyn, shadow), 3 ((a - b)^2), 8 (u u + v v with u, v
+    sums held to the squares' own size: 3 each, the sum 1, slack 1)."""
+    own = {"dyn": 0.0, "shadow": 0.0, "feat": 3.0, "cycle": 8.0}[name]
+    return float(-(-n // stride) + 6 + 4 + 3 + 3) + own

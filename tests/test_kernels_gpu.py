@@ -666,6 +666,14 @@ def test_pixel_loss_matches_torch(hip_lib, R):
     np.testing.assert_allclose(float(loss), float(want), rtol=2e-6)
     np.testing.assert_allclose(rd.grad.cpu().numpy(), r2.grad.numpy(), rtol=1e-5, atol=1e-9)
     np.testing.assert_allclose(od.grad.cpu().numpy(), o2.grad.numpy(), rtol=1e-5, atol=1e-9)
+    if R <= 777:   # every gradient entry inside its first-order fp64 bound (tests/_bounds.pixel_bounds), the total inside the sum of the per-ray bounds
+        from tests import _loss_probe as LP
+        from tests._bounds import U, assert_err_bound, pixel_bounds
+        st = LP.restate_pixel(rgb.numpy(), pix.numpy(), opa.numpy().reshape(-1), sky.numpy(), 1.0, 0.001, up=1024.0)
+        bd = pixel_bounds(st)
+        assert_err_bound(rd.grad.cpu().numpy(), st["d_rgb"], bd["d_rgb"], f"pixel_loss R={R} d_rgb")
+        assert_err_bound(od.grad.cpu().numpy(), st["d_opa"], bd["d_opa"], f"pixel_loss R={R} d_opacity")
+        assert abs(float(loss) - st["total"]) <= bd["rays"].sum() + U * abs(st["total"])
 
 
 @pytest.mark.parametrize("R,S,E,terms", [(64, 16, 8, "dsfc"), (8192, 128, 64, "dsfc"), (777, 33, 5, "dc"), (1000, 64, 64, "f"),
@@ -718,6 +726,24 @@ def test_reg_losses_match_the_reference_expressions(hip_lib, R, S, E, terms):
     # run-to-run bit-stable (fixed summation order)
     again = ops.reg_losses(leaves["base"].detach(), grad_scale=scale, **{k: v.detach() for k, v in kw.items()})
     assert torch.equal(again, out.detach())
+    if R <= 777:   # every gradient entry within its few roundings of fp64, the total inside the sum of the block partials' abs-sum bounds
+        from tests import _loss_probe as LP
+        from tests._bounds import U
+        T = {}
+        if "d" in terms:
+            T["dyn"] = dyn.numpy()
+        if "s" in terms:
+            T["shadow"] = sh.numpy()
+        if "f" in terms:
+            T.update(feat=ft.numpy(), feat_gt=gt.numpy())
+        if "c" in terms:
+            T.update(ff=ff.numpy(), fpb=fpb.numpy(), bf=bf.numpy(), bpf=bpf.numpy())
+        b = dict(T=T, coefs=dict(dyn=0.01, shadow=0.01, feat=0.5, cycle=0.005), base=float(base), up=1.0, grad_scale=scale)
+        b["ref"] = LP.restate_reg(T, b["coefs"], b["base"], 1.0, scale)
+        got = {n: leaves[k].grad.cpu().numpy() for n, k in (("dyn", "dyn"), ("shadow", "sh"), ("feat", "ft"), ("fpb", "fpb"), ("bpf", "bpf")) if k in used}
+        LP.check_reg_realistic(b, None, float(out), got, f"reg_losses R={R} S={S} E={E} {terms}")
+        err = LP.reg_block_refs(b)[1]
+        assert abs(float(out) - b["ref"]["total"]) <= err.sum() + U * abs(b["ref"]["total"])
 
 
 @pytest.mark.parametrize("R,m,n,unbounded,want_pos,jit", [(8192, 129, 64, True, False, True), (100, 2, 128, True, True, True),
@@ -782,6 +808,19 @@ def test_reg_losses_flow_pair_equals_the_four_slices(hip_lib, R, S, terms):
     assert flow.grad is None and f_ref.grad is None
     assert torch.equal(flow2.grad, f2_ref.grad)
     assert float(flow2.grad[:N, :3].abs().max()) == 0.0 and float(flow2.grad[N:, 3:].abs().max()) == 0.0
+    if R <= 777:   # the packed form held directly to fp64, not only to the sliced form
+        from tests import _loss_probe as LP
+        from tests._bounds import U
+        T = dict(flow6=flow.detach().cpu().numpy().reshape(-1, 6), flow2=flow2.detach().cpu().numpy())
+        if "d" in terms:
+            T["dyn"] = dyn.cpu().numpy()
+        if "s" in terms:
+            T["shadow"] = sh.cpu().numpy()
+        b = dict(T=T, coefs=dict(dyn=0.01, shadow=0.01, feat=0.5, cycle=0.005), base=float(base), up=1.0, grad_scale=1024.0)
+        b["ref"] = LP.restate_reg(T, b["coefs"], b["base"], 1.0, 1024.0)
+        LP.check_reg_realistic(b, None, float(out), dict(flow2=flow2.grad.cpu().numpy()), f"reg_losses flow_pair R={R} S={S} {terms}")
+        err = LP.reg_block_refs(b)[1]
+        assert abs(float(out) - b["ref"]["total"]) <= err.sum() + U * abs(b["ref"]["total"])
 
 
 def test_reg_losses_argument_errors(hip_lib):
@@ -952,22 +991,33 @@ def test_lidar_loss_matches_reference_form(hip_lib, R, S):
 
     d64, w64 = depth.double().requires_grad_(True), w.double().requires_grad_(True)
     g64, t64 = gt.double().squeeze(-1), t.double()
-    valid = (g64 > 0.01) & (g64 < 80.0)
+    # the masks are integer facts: taken from the fp32 comparisons the reference itself performs (fp32 tensors against fl32(gt -+ eps))
+    valid = (gt.squeeze(-1) > 0.01) & (gt.squeeze(-1) < 80.0)
     norm = lambda v: torch.clamp(v / 80.0, 0.0, 1.0)  # noqa: E731
     depth_loss = ((norm(d64.squeeze(-1)[valid]) - norm(g64[valid])) ** 2).mean() if bool(valid.any()) else torch.zeros((), dtype=torch.float64)
     gd = g64.unsqueeze(-1)
-    empty = t64 < gd - eps
-    near = (t64 > gd - eps) & (t64 < gd + eps)
+    empty = t < gt - eps
+    near = (t > (gt - eps)) & (t < gt + eps)
     sigma = eps / 3
     delta = (1 / math.sqrt(2 * math.pi * sigma ** 2)) * torch.exp(-((t64 - gd) ** 2) / (2 * sigma ** 2))
     empty_loss = (w64.square() * empty).sum(-1, keepdim=True).mean()
     near_loss = ((w64 - delta).square() * near).sum(-1, keepdim=True).mean()
-    sight = ((empty_loss + near_loss) * (g64 > 0)).mean() * coef
+    sight = ((empty_loss + near_loss) * (gt.squeeze(-1) > 0)).mean() * coef
     want = depth_loss + sight
     (want * 3.0).backward()
     np.testing.assert_allclose(float(loss), float(want), rtol=2e-5)
     np.testing.assert_allclose(dd.grad.cpu().numpy(), d64.grad.numpy(), rtol=1e-4, atol=1e-9)
     np.testing.assert_allclose(wd.grad.cpu().numpy(), w64.grad.numpy(), rtol=1e-4, atol=1e-7 * float(w64.grad.abs().max()))
+    if R <= 777:   # every gradient entry inside its first-order fp64 bound (tests/_bounds.lidar_bounds), the total inside the sum of the per-ray bounds
+        from tests import _loss_probe as LP
+        from tests._bounds import U, assert_err_bound, lidar_bounds
+        st = LP.restate_lidar(depth.numpy(), gt.numpy(), w.numpy(), t.numpy(), eps, 80.0, 1.0, coef, up=3.0)
+        if st["n_valid"]:
+            np.testing.assert_allclose(st["total_ref"], float(want), rtol=1e-12)
+        bd = lidar_bounds(st, eps)
+        assert_err_bound(dd.grad.cpu().numpy(), st["d_depth"], bd["d_depth"], f"lidar_loss R={R} S={S} d_depth")
+        assert_err_bound(wd.grad.cpu().numpy(), st["d_w"], bd["d_w"], f"lidar_loss R={R} S={S} d_weights")
+        assert abs(float(loss) - st["total"]) <= bd["rays"].sum() + U * abs(st["total"])
 
 
 @pytest.mark.parametrize("R,S,with_shadow", [(3, 16, True), (257, 128, True), (100, 70, False)])

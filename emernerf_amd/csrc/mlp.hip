@@ -1,4 +1,4 @@
-// Small-MLP head kernels for gfx950 on the fp32-input matrix cores.
+// Small-MLP head kernels for gfx950 on the fp32-input matrix cores, and the weight-gradient kernels of every head.
 //
 // Replaces the torch.nn.Linear (+ReLU / Sigmoid / trunc_exp) chains of the reference's heads
 // (radiance_fields/radiance_field.py:74-198, radiance_fields/mlp.py:7-46), i.e. one cuBLAS GEMM plus
@@ -7,26 +7,30 @@
 // Precision: v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 -- f32 in, f32 accumulate, bit-identical
 // to a k-ordered fmaf chain (MI355X guide, "FP32-input MFMA"), so the heads keep the reference's
 // fp32 semantics while running on the matrix pipe at the full fp32 rate and leaving the VALU free
-// for bias/activation epilogues.  Tests: tests/test_head_exact_gpu.py (exact grid probes, the
-// trunc_exp clamp) and the per-entry bounds of tests/_bounds.py.
+// for bias/activation epilogues; the streamed dW kernel uses bf16x3 (csrc/bf16x3.h) with fp32-equivalent results.
+// Tests: tests/test_head_exact_gpu.py (exact grid probes, the trunc_exp clamp), tests/test_wgrad_exact_gpu.py (integer
+// probes of emer_wgrad_segmented) and the per-entry bounds of tests/_bounds.py.
 //
 // Kernels
-//   linear_fwd  : Y = act(X W^T + b).  128-row workgroup tile, 4 waves x 32 rows; 64-wide (32x32x2)
-//                 or 16-wide (16x16x4, for 1/3/6-channel outputs) column tiles; X/W K-chunks of 32
-//                 staged in LDS with an odd (33) / even-offset (34) row pitch so every ds_read_b32
-//                 lane group is bank-conflict free.  Generic B strides serve dX = dPre W as well.
-//   act_bwd     : dPre = dY * act'(Y)  (act' from the saved output only).
-//   linear_dw   : dW += dPre^T X, db += colsum(dPre): split over rows, 32-row LDS tiles, per-wave
-//                 32x32 output tiles held in accumulators for the whole row range, one fp32 atomic
-//                 pass per workgroup at the end.
+//   linear_fwd        : Y = act(X W^T + b).  128-row workgroup tile, 4 waves x 32 rows; 64-wide (32x32x2) or 16-wide
+//                       (16x16x4, for 1/3/6-channel outputs) column tiles; X/W K-chunks of 32 staged in LDS with an odd
+//                       (33) / even-offset (34) row pitch so every ds_read_b32 lane group is bank-conflict free.  Generic
+//                       B strides serve dX = dPre W as well, with dPre = dY * act'(Y) formed while the A tile is staged.
+//   linear_dw         : partial dW = dPre^T X, db = colsum(dPre) per row block, dPre formed while staging (emer_linear_bwd).
+//   wgrad_seg         : the same for a given dPre and a segmented X (row-major, level-major, per-ray: emer_wgrad_segmented).
+//                       Twins: 32-row LDS tiles, per-wave 32x32 output tiles held in accumulators for the whole row
+//                       range, plain stores of the partial; they differ in how a tile's operands are fetched.
+//   wgrad_stream      : emer_wgrad_segmented without per-ray operands: bf16x3, operands stream from HBM into the MFMA layout.
+//   linear_dw_reduce_multi : sums the row blocks' partials into dW / db (one fp32 atomic per entry and range of blocks); every
+//                       weight gradient of this file and of csrc/mlp_fused.hip ends here (launch_dw_reduce[_multi]).
+//   mlp_chain         : up to EMER_CHAIN_MAX_LAYERS dense layers on 16-row tiles, one wave per tile, weights in LDS.
 #include "common.h"
+#include "bf16x3.h"
 
 #include <type_traits>
 
 namespace emer {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ float apply_act(int act, float x) {
     switch (act) {
@@ -147,12 +151,17 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float *__restrict
     }
 }
 
-// dW[N,K] += dPre[M,N]^T X[M,K];  db[N] += colsum(dPre), with dPre = dY * act'(Y) formed while staging.
-// grid = (row blocks, K groups, N groups).  A workgroup reduces `rows_per_block` rows: 32-row tiles are
-// prefetched into registers while the previous tile feeds the MFMAs out of LDS; its (NG/32)*(KG/32)
-// output tiles are dealt round-robin to the 4 waves (TPW per wave) and live in accumulators for the whole
+// ------------------------------------------------------------------------------------------------ LDS-staged dW
+// dW[N,K] += D[M,N]^T X[M,K];  db[N] += colsum(D).  grid = (row blocks, K groups, N groups).  A workgroup reduces
+// `rows_per_block` rows: 32-row tiles are prefetched into registers while the previous tile feeds the MFMAs out of LDS; its
+// (NG/32)*(KG/32) output tiles are dealt round-robin to the 4 waves (TPW per wave) and live in accumulators for the whole
 // row range.  Partial results go to a workspace [row block][N*K + N] with plain stores; a second kernel
 // sums the row blocks (L2 float atomics retire only ~21 G/s on this chip, see tools/atomic_probe.hip).
+// linear_dw_kernel and wgrad_seg_kernel are TWINS: they differ in their `fetch` only, and tiles, loop, MFMA sweep, bias sum and the store of
+// the partial are written out in both.  Every shared form of that body that was tried moved hipcc's register allocation of the loader
+// ("Shared stages of `csrc/mlp.hip`"): a fix to one copy goes into the other as well.
+// emer_linear_bwd: D = dY * act'(Y) (+ the density side gradient on column 0), formed while staging; X is a plain matrix.
+// Twin of wgrad_seg_kernel below (everything but `fetch`).
 template <int NGT, int KGT>  // NG = 32*NGT output rows (n), KG = 32*KGT output columns (k) per workgroup
 __global__ __launch_bounds__(256) void linear_dw_kernel(const float *__restrict__ dy, int64_t lddy, const float *__restrict__ ysave,
                                                         int64_t ldy, int act, const float *__restrict__ d_aux,
@@ -242,54 +251,128 @@ __global__ __launch_bounds__(256) void linear_dw_kernel(const float *__restrict_
     if (want_bias && blockIdx.y == 0 && wave == 0 && lane < NG && n_base + lane < N) part[(int64_t)N * K + n_base + lane] = bsum;
 }
 
-// dw[i] += sum_b partials[b][i]  (i < N*K),  dbias[i - N*K] += ...  (i >= N*K).
-// The partial blocks are cut into gridDim.y ranges so that the (small) N*K + N extent still fills the chip; each
+// emer_wgrad_segmented: D = dPre as given (column 0 from sx.col0 when non-null); X is the virtual concatenation of the segments.
+// Twin of linear_dw_kernel above (everything but `fetch`).
+struct SegX { emer_chain_seg s[EMER_CHAIN_MAX_SEGS]; int32_t n; const float *col0; };
+
+template <int NGT, int KGT>
+__global__ __launch_bounds__(256) void wgrad_seg_kernel(const float *__restrict__ dpre, int64_t ldd, const SegX sx,
+                                                        float *__restrict__ partials, int64_t M, int32_t N, int32_t K,
+                                                        int32_t rows_per_block, int want_bias) {
+    constexpr int NG = 32 * NGT, KG = 32 * KGT, TILES = NGT * KGT, TPW = (TILES + 3) / 4;
+    constexpr int ND = (32 * NG) / 256, NX = (32 * KG) / 256;
+    __shared__ float ds[32 * NG];
+    __shared__ float xs[32 * KG];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int32_t n_base = blockIdx.z * NG, k_base = blockIdx.y * KG;
+    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r_end = (r_begin + rows_per_block < M) ? r_begin + rows_per_block : M;
+    f32x16 acc[TPW];
+#pragma unroll
+    for (int j = 0; j < TPW; ++j) acc[j] = f32x16{0};
+    float bsum = 0.0f;
+    float dreg[ND], xreg[NX];
+    int fl[EMER_CHAIN_MAX_SEGS];
+#pragma unroll
+    for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) fl[s] = __ffs(sx.s[s].f > 0 ? sx.s[s].f : 1) - 1;
+    auto fetch = [&](int64_t r0) {
+        int64_t ray0[EMER_CHAIN_MAX_SEGS];
+        int32_t rem0[EMER_CHAIN_MAX_SEGS];
+#pragma unroll
+        for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) {  // per-ray operands: ONE scalar division per segment per 32-row tile
+            const int32_t rd = sx.s[s].row_div > 0 ? sx.s[s].row_div : 1;
+            ray0[s] = (rd == 1) ? r0 : r0 / rd;
+            rem0[s] = (int32_t)(r0 - ray0[s] * rd);
+        }
+#pragma unroll
+        for (int i = 0; i < ND; ++i) {
+            const int idx = tid + i * 256;
+            const int r = idx / NG, c = idx % NG;
+            const int64_t gr = r0 + r;
+            const int32_t gn = n_base + c;
+            dreg[i] = (gr < r_end && gn < N) ? ((sx.col0 && gn == 0) ? sx.col0[gr] : dpre[gr * ldd + gn]) : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            const int idx = tid + i * 256;
+            const int r = idx / KG, c = idx % KG;
+            const int64_t gr = r0 + r;
+            const int32_t gk = k_base + c;
+            float v = 0.0f;
+            if (gr < r_end && gk < K) {
+#pragma unroll
+                for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) {
+                    if (s < sx.n && gk >= sx.s[s].col && gk < sx.s[s].col + sx.s[s].width) {
+                        const int32_t c = gk - sx.s[s].col;
+                        if (sx.s[s].mode == 1) {
+                            v = sx.s[s].ptr[((int64_t)(c >> fl[s]) * sx.s[s].n_total + gr) * sx.s[s].f + (c & (sx.s[s].f - 1))];
+                        } else if (sx.s[s].row_div == 1) {
+                            v = sx.s[s].ptr[gr * sx.s[s].ld + c];
+                        } else {  // per-ray operand (32 <= row_div in practice: at most one ray boundary inside a tile)
+                            const int32_t rem = rem0[s] + r;
+                            const int64_t ray = rem < sx.s[s].row_div ? ray0[s] : ray0[s] + rem / sx.s[s].row_div;
+                            v = sx.s[s].ptr[ray * sx.s[s].ld + c];
+                        }
+                    }
+                }
+            }
+            xreg[i] = v;
+        }
+    };
+    fetch(r_begin);
+    for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
+#pragma unroll
+        for (int i = 0; i < ND; ++i) ds[tid + i * 256] = dreg[i];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xs[tid + i * 256] = xreg[i];
+        __syncthreads();
+        if (r0 + 32 < r_end) fetch(r0 + 32);
+#pragma unroll
+        for (int j = 0; j < TPW; ++j) {
+            const int t = wave + 4 * j;
+            if (t < TILES) {  // wave-uniform
+                const int nt = t / KGT, kt = t % KGT;
+                const float *ap = ds + (lane >> 5) * NG + nt * 32 + (lane & 31);
+                const float *bp = xs + (lane >> 5) * KG + kt * 32 + (lane & 31);
+#pragma unroll 4
+                for (int s = 0; s < 16; ++s)
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s * NG], bp[2 * s * KG], acc[j], 0, 0, 0);
+            }
+        }
+        if (want_bias && blockIdx.y == 0 && wave == 0 && lane < NG) {
+#pragma unroll 8
+            for (int r = 0; r < 32; ++r) bsum += ds[r * NG + lane];
+        }
+        __syncthreads();
+    }
+    float *__restrict__ part = partials + (int64_t)blockIdx.x * ((int64_t)N * K + N);
+#pragma unroll
+    for (int j = 0; j < TPW; ++j) {
+        const int t = wave + 4 * j;
+        if (t >= TILES) continue;
+        const int nt = t / KGT, kt = t % KGT;
+        const int32_t k = k_base + kt * 32 + (lane & 31);
+        if (k >= K) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int32_t n = n_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (n < N) part[(int64_t)n * K + k] = acc[j][r];
+        }
+    }
+    if (want_bias && blockIdx.y == 0 && wave == 0 && lane < NG && n_base + lane < N) part[(int64_t)N * K + n_base + lane] = bsum;
+}
+
+// ------------------------------------------------------------------------------------------------ sum of the partials
+// dw[i] += sum_b partials[b][off + i]  (i < n*k),  dbias[i - n*k] += ...  (i >= n*k), for up to EMER_DW_MAX_JOBS (dW | dbias) pairs of
+// ONE partial buffer in one launch (blockIdx.z = job): the fused backward kernels leave two or three gradients in each workgroup's
+// partial, and three 5-us launches in a row cost more than the sums themselves.
+// The partial blocks are cut into gridDim.y ranges so that the (small) n*k + n extent still fills the chip; each
 // thread sums its range with four independent accumulators (loads in flight) and merges with one f32 atomic.
 struct DwDst {  // where column k of the (virtually concatenated) operand lands in dw: dw[n * ld + dst + (k - col)]
     int32_t col[EMER_CHAIN_MAX_SEGS], width[EMER_CHAIN_MAX_SEGS], dst[EMER_CHAIN_MAX_SEGS];
     int32_t n, K;
     int64_t ld;
 };
-static inline DwDst dw_dst_identity(int32_t k) {
-    DwDst d;
-    for (int i = 0; i < EMER_CHAIN_MAX_SEGS; ++i) { d.col[i] = 0; d.width[i] = 0; d.dst[i] = 0; }
-    d.col[0] = 0; d.width[0] = k; d.dst[0] = 0; d.n = 1; d.K = k; d.ld = k;
-    return d;
-}
-
-__global__ __launch_bounds__(256) void linear_dw_reduce_kernel(const float *__restrict__ partials, int32_t n_blocks, int64_t stride,
-                                                               int64_t nk, float *__restrict__ dw, float *__restrict__ dbias, const DwDst dst,
-                                                               int64_t extent = -1) {
-    // extent: floats of a partial that belong to this (dW | dbias) pair; -1: the whole partial (= stride)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (extent < 0 ? stride : extent)) return;
-    const int32_t per = (n_blocks + (int32_t)gridDim.y - 1) / (int32_t)gridDim.y;
-    const int32_t b0 = (int32_t)blockIdx.y * per;
-    const int32_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    const float *__restrict__ p = partials + i;
-    int32_t b = b0;
-    for (; b + 4 <= b1; b += 4) {
-        a0 += p[(int64_t)b * stride];
-        a1 += p[(int64_t)(b + 1) * stride];
-        a2 += p[(int64_t)(b + 2) * stride];
-        a3 += p[(int64_t)(b + 3) * stride];
-    }
-    for (; b < b1; ++b) a0 += p[(int64_t)b * stride];
-    const float a = (a0 + a1) + (a2 + a3);
-    if (b0 >= b1) return;
-    if (i < nk) {
-        const int32_t n = (int32_t)(i / dst.K), k = (int32_t)(i - (int64_t)n * dst.K);
-        int64_t o = -1;
-#pragma unroll
-        for (int sg = 0; sg < EMER_CHAIN_MAX_SEGS; ++sg)
-            if (sg < dst.n && k >= dst.col[sg] && k < dst.col[sg] + dst.width[sg]) o = (int64_t)n * dst.ld + dst.dst[sg] + (k - dst.col[sg]);
-        if (o >= 0) __hip_atomic_fetch_add(dw + o, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (dbias) __hip_atomic_fetch_add(dbias + (i - nk), a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// [r4] Several (dW | dbias) pairs of ONE partial buffer in one launch (blockIdx.z = job): the fused backward kernels leave two or three
-// gradients in each workgroup's partial, and three 5-us launches in a row cost more than the sums themselves.
 struct DwJobs {
     int32_t n_jobs;
     int64_t off[EMER_DW_MAX_JOBS], nk[EMER_DW_MAX_JOBS], extent[EMER_DW_MAX_JOBS];   // start inside a partial, floats of dW, floats of dW + dbias
@@ -333,10 +416,53 @@ static inline uint32_t dw_reduce_splits(int32_t n_blocks, int64_t stride) {
     return (uint32_t)(s < 1 ? 1 : s);
 }
 
+// The one launch of the reduction.  `span`: floats of a partial that the grid (and the split rule) is sized for; 0: the largest job.
+static int launch_reduce(const float *partials, int32_t n_blocks, int64_t stride, int n_jobs, const DwReduceJob *jb, int64_t span,
+                         const char *what, hipStream_t st) {
+    DwJobs jobs;
+    jobs.n_jobs = n_jobs;
+    int64_t max_extent = 0;
+    for (int j = 0; j < EMER_DW_MAX_JOBS; ++j) {
+        const bool on = j < n_jobs;
+        const DwReduceJob &q = jb[on ? j : 0];
+        DwDst &d = jobs.dst[j];   // n_segs == 0: one block, column c of the partial at dw[row * ld_dw + c]
+        for (int i = 0; i < EMER_CHAIN_MAX_SEGS; ++i) {
+            const bool seg = i < q.n_segs;
+            d.col[i] = seg ? q.col[i] : 0; d.width[i] = seg ? q.width[i] : (i == 0 && q.n_segs <= 0 ? q.k : 0); d.dst[i] = seg ? q.dst[i] : 0;
+        }
+        d.n = q.n_segs > 0 ? q.n_segs : 1; d.K = q.k; d.ld = q.ld_dw;
+        jobs.off[j] = q.off; jobs.nk[j] = (int64_t)q.n * q.k; jobs.extent[j] = on ? (int64_t)q.n * q.k + (q.db ? q.n : 0) : 0;
+        jobs.dw[j] = q.dw; jobs.dbias[j] = q.db;
+        if (jobs.extent[j] > max_extent) max_extent = jobs.extent[j];
+    }
+    if (span <= 0) span = max_extent;
+    hipLaunchKernelGGL(linear_dw_reduce_multi_kernel, dim3((uint32_t)ceil_div(span, 256), dw_reduce_splits(n_blocks, span), (uint32_t)n_jobs),
+                       dim3(256), 0, st, partials, n_blocks, stride, jobs);
+    return check_launch(what);
+}
+
+// Up to EMER_DW_MAX_JOBS gradients of one partial buffer in one launch.  Job j: dW [n][k] (+ dbias [n] when db != null) at float `off`
+// of every partial; `n_segs` == 0: dW goes to dw[row * ld + column]; else column block s = columns col[s] .. col[s] + width[s] - 1 lands
+// at dw[row * ld_dw + dst[s] ..].
+int launch_dw_reduce_multi(const float *partials, int32_t n_blocks, int64_t stride, int n_jobs, const DwReduceJob *jb, hipStream_t st) {
+    return launch_reduce(partials, n_blocks, stride, n_jobs, jb, 0, "dw_reduce_multi", st);
+}
+
+// One gradient whose partial starts with dW [n][k] | dbias [n] (the grid covers both parts whether or not dbias is wanted).
+static int launch_dw_reduce_job(const float *partials, int32_t n_blocks, int64_t stride, const DwReduceJob &job, const char *what, hipStream_t st) {
+    return launch_reduce(partials, n_blocks, stride, 1, &job, (int64_t)job.n * job.k + job.n, what, st);
+}
+// Sum `n_blocks` partials (`stride` floats apart, each holding dW [n][k] | dbias [n] at its start) into dw (+=, leading dimension
+// ld_dw) and dbias (+=, may be null).  Used by the fused backward kernels of csrc/mlp_fused.hip.
+int launch_dw_reduce(const float *partials, int32_t n_blocks, int64_t stride, int32_t n, int32_t k, float *dw, int64_t ld_dw,
+                     float *dbias, hipStream_t st) {
+    return launch_dw_reduce_job(partials, n_blocks, stride, DwReduceJob{0, n, k, dw, ld_dw, dbias, 0, {0}, {0}, {0}}, "dw_reduce", st);
+}
+
 // Rows per workgroup of the dW kernels.  Big tiles hold few waves per SIMD (their accumulators fill the register
 // file), so they want long row ranges (fewer partials, longer streams): 64x128 -> 4096 rows, 64 x (<=64) -> 2048, n <= 32 ->
 // 1024.  Never fewer than ~512 workgroups' worth of parallelism for per-ray heads (8192 rows would otherwise occupy 8
-// CUs).  emer_linear_bwd_workspace uses the same rule.
+// CUs).
 static inline int32_t dw_rows_per_block(int64_t m, int32_t n, int32_t k) {
     const int tiles = ((n + 31) / 32) * ((k + 31) / 32);
     const int64_t cap = tiles >= 6 ? 4096 : (n > 32 ? 2048 : 1024);
@@ -347,56 +473,33 @@ static inline int32_t dw_rows_per_block(int64_t m, int32_t n, int32_t k) {
     return (int32_t)r;
 }
 
-// Sum `n_blocks` partials (`stride` floats apart, each holding dW [n][k] | dbias [n] at its start) into dw (+=, leading dimension
-// ld_dw) and dbias (+=, may be null).  Used by the fused backward kernels of csrc/mlp_fused.hip.
-int launch_dw_reduce(const float *partials, int32_t n_blocks, int64_t stride, int32_t n, int32_t k, float *dw, int64_t ld_dw,
-                     float *dbias, hipStream_t st) {
-    DwDst d = dw_dst_identity(k);
-    d.ld = ld_dw;
-    const int64_t extent = (int64_t)n * k + n;
-    hipLaunchKernelGGL(linear_dw_reduce_kernel, dim3((uint32_t)ceil_div(extent, 256), dw_reduce_splits(n_blocks, extent)), dim3(256), 0, st, partials,
-                       n_blocks, stride, (int64_t)n * k, dw, dbias, d, extent);
-    return check_launch("dw_reduce");
+// Tile plan of a dW launch: the workgroup tile of the LDS-staged kernels, the row blocks (= partials) and their grid.
+struct DwPlan {
+    int32_t NG, KG, rpb, n_row_blocks;
+    dim3 grid;
+};
+static inline DwPlan dw_plan(int64_t m, int32_t n, int32_t k) {
+    DwPlan p;
+    p.NG = n <= 32 ? 32 : 64;
+    p.KG = k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256));
+    p.rpb = dw_rows_per_block(m, n, k);
+    p.n_row_blocks = (int32_t)ceil_div(m, p.rpb);
+    p.grid = dim3((uint32_t)p.n_row_blocks, (uint32_t)ceil_div(k, p.KG), (uint32_t)ceil_div(n, p.NG));
+    return p;
 }
-
-// The same for a partial whose column blocks go to different places: block s = columns col[s] .. col[s] + width[s] - 1 of the [n][k]
-// partial lands at dw[row * ld_dw + dst[s] ..]; no bias part.
-int launch_dw_reduce_cols(const float *partials, int32_t n_blocks, int64_t stride, int32_t n, int32_t k, float *dw, int64_t ld_dw,
-                          int32_t n_segs, const int32_t *col, const int32_t *width, const int32_t *dst, hipStream_t st) {
-    DwDst d = dw_dst_identity(k);
-    d.ld = ld_dw;
-    d.n = n_segs;
-    for (int i = 0; i < n_segs && i < EMER_CHAIN_MAX_SEGS; ++i) { d.col[i] = col[i]; d.width[i] = width[i]; d.dst[i] = dst[i]; }
-    const int64_t extent = (int64_t)n * k;
-    hipLaunchKernelGGL(linear_dw_reduce_kernel, dim3((uint32_t)ceil_div(extent, 256), dw_reduce_splits(n_blocks, extent)), dim3(256), 0, st, partials,
-                       n_blocks, stride, (int64_t)n * k, dw, (float *)nullptr, d, extent);
-    return check_launch("dw_reduce_cols");
-}
-
-// Up to EMER_DW_MAX_JOBS gradients of one partial buffer in one launch.  Job j: dW [n][k] (+ dbias [n] when db != null) at float `off`
-// of every partial; `n_segs` == 0: dW goes to dw[row * ld + column]; else its column blocks are scattered as in launch_dw_reduce_cols.
-int launch_dw_reduce_multi(const float *partials, int32_t n_blocks, int64_t stride, int n_jobs, const DwReduceJob *jb, hipStream_t st) {
-    DwJobs jobs;
-    jobs.n_jobs = n_jobs;
-    int64_t max_extent = 0;
-    for (int j = 0; j < EMER_DW_MAX_JOBS; ++j) {
-        const bool on = j < n_jobs;
-        const DwReduceJob &q = jb[on ? j : 0];
-        DwDst d = dw_dst_identity(q.k);
-        d.ld = q.ld_dw;
-        if (q.n_segs > 0) {
-            d.n = q.n_segs;
-            for (int i = 0; i < q.n_segs && i < EMER_CHAIN_MAX_SEGS; ++i) { d.col[i] = q.col[i]; d.width[i] = q.width[i]; d.dst[i] = q.dst[i]; }
-        }
-        jobs.dst[j] = d;
-        jobs.off[j] = q.off; jobs.nk[j] = (int64_t)q.n * q.k; jobs.extent[j] = on ? (int64_t)q.n * q.k + (q.db ? q.n : 0) : 0;
-        jobs.dw[j] = q.dw; jobs.dbias[j] = q.db;
-        if (jobs.extent[j] > max_extent) max_extent = jobs.extent[j];
-    }
-    hipLaunchKernelGGL(linear_dw_reduce_multi_kernel, dim3((uint32_t)ceil_div(max_extent, 256), dw_reduce_splits(n_blocks, max_extent), (uint32_t)n_jobs),
-                       dim3(256), 0, st, partials, n_blocks, stride, jobs);
-    return check_launch("dw_reduce_multi");
-}
+// KERNEL<NG / 32, KG / 32> on the plan's grid
+#define EMER_DW_LAUNCH(KERNEL, A, B, P, ST, ...) hipLaunchKernelGGL((KERNEL<A, B>), (P).grid, dim3(256), 0, ST, __VA_ARGS__)
+#define EMER_DW_DISPATCH(KERNEL, P, ST, ...)                                                                                     \
+    do {                                                                                                                         \
+        const int kgt_ = (P).KG / 32;                                                                                            \
+        if ((P).NG == 32) {                                                                                                      \
+            if (kgt_ == 1) EMER_DW_LAUNCH(KERNEL, 1, 1, P, ST, __VA_ARGS__); else if (kgt_ == 2) EMER_DW_LAUNCH(KERNEL, 1, 2, P, ST, __VA_ARGS__); \
+            else if (kgt_ == 4) EMER_DW_LAUNCH(KERNEL, 1, 4, P, ST, __VA_ARGS__); else EMER_DW_LAUNCH(KERNEL, 1, 8, P, ST, __VA_ARGS__);           \
+        } else {                                                                                                                 \
+            if (kgt_ == 1) EMER_DW_LAUNCH(KERNEL, 2, 1, P, ST, __VA_ARGS__); else if (kgt_ == 2) EMER_DW_LAUNCH(KERNEL, 2, 2, P, ST, __VA_ARGS__); \
+            else if (kgt_ == 4) EMER_DW_LAUNCH(KERNEL, 2, 4, P, ST, __VA_ARGS__); else EMER_DW_LAUNCH(KERNEL, 2, 8, P, ST, __VA_ARGS__);           \
+        }                                                                                                                        \
+    } while (0)
 
 static int launch_linear(const float *x, int64_t ldx, const float *w, int64_t sbj, int64_t sbk, const float *bias, float *y,
                          int64_t ldy, int64_t M, int32_t N, int32_t K, int act, float *aux, hipStream_t st,
@@ -430,7 +533,7 @@ extern "C" int emer_linear_fwd(const float *x, int64_t ldx, const float *w, cons
 // floats of workspace emer_linear_bwd needs for the dW / dbias partial sums (0 when dw is not requested)
 extern "C" int64_t emer_linear_bwd_workspace(int64_t m, int32_t n, int32_t k) {
     if (m <= 0 || n <= 0 || k <= 0) return 0;
-    return ceil_div(m, dw_rows_per_block(m, n, k)) * ((int64_t)n * k + n);
+    return dw_plan(m, n, k).n_row_blocks * ((int64_t)n * k + n);
 }
 
 extern "C" int emer_linear_bwd(const float *dy, int64_t lddy, const float *y, int64_t ldy, const float *x, int64_t ldx,
@@ -454,22 +557,11 @@ extern "C" int emer_linear_bwd(const float *dy, int64_t lddy, const float *y, in
     }
     if (dw) {
         EMER_REQUIRE(x && ldx >= k && workspace, "linear_bwd: dw requested but x / workspace missing or ldx too small");
-        const int32_t NG = n <= 32 ? 32 : 64;
-        const int32_t KG = k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256));
-        const int32_t rpb = dw_rows_per_block(m, n, k);
-        const int32_t n_row_blocks = (int32_t)ceil_div(m, rpb);
-        const dim3 grid((uint32_t)n_row_blocks, (uint32_t)ceil_div(k, KG), (uint32_t)ceil_div(n, NG));
-#define EMER_DW(A, B) hipLaunchKernelGGL((linear_dw_kernel<A, B>), grid, dim3(256), 0, st, dy, lddy, ya, ldy, act, d_aux_density, \
-                                         aux_density, x, ldx, workspace, m, n, k, rpb, dbias ? 1 : 0)
-        if (NG == 32) { if (KG == 32) EMER_DW(1, 1); else if (KG == 64) EMER_DW(1, 2); else if (KG == 128) EMER_DW(1, 4); else EMER_DW(1, 8); }
-        else          { if (KG == 32) EMER_DW(2, 1); else if (KG == 64) EMER_DW(2, 2); else if (KG == 128) EMER_DW(2, 4); else EMER_DW(2, 8); }
-#undef EMER_DW
+        const DwPlan p = dw_plan(m, n, k);
+        EMER_DW_DISPATCH(linear_dw_kernel, p, st, dy, lddy, ya, ldy, act, d_aux_density, aux_density, x, ldx, workspace, m, n, k, p.rpb, dbias ? 1 : 0);
         if (int rc = check_launch("linear_dw")) return rc;
-        const int64_t stride = (int64_t)n * k + n;
-        const DwDst ddst = dw_dst_identity(k);
-        hipLaunchKernelGGL(linear_dw_reduce_kernel, dim3((uint32_t)ceil_div(stride, 256), dw_reduce_splits(n_row_blocks, stride)), dim3(256), 0, st, workspace, n_row_blocks,
-                           stride, (int64_t)n * k, dw, dbias, ddst);
-        if (int rc = check_launch("linear_dw_reduce")) return rc;
+        if (int rc = launch_dw_reduce_job(workspace, p.n_row_blocks, (int64_t)n * k + n, DwReduceJob{0, n, k, dw, k, dbias, 0, {0}, {0}, {0}}, "linear_dw_reduce", st))
+            return rc;
     }
     return EMER_OK;
 }
@@ -673,116 +765,6 @@ __global__ __launch_bounds__(1024) void mlp_chain_kernel(const emer_chain_desc d
     }
 }
 
-// dW kernel with a segmented (virtual concat) X operand; dPre is given materialised.
-struct SegX { emer_chain_seg s[EMER_CHAIN_MAX_SEGS]; int32_t n; const float *col0; };  // col0: replaces column 0 of dPre when non-null
-
-template <int NGT, int KGT>
-__global__ __launch_bounds__(256) void wgrad_seg_kernel(const float *__restrict__ dpre, int64_t ldd, const SegX sx,
-                                                        float *__restrict__ partials, int64_t M, int32_t N, int32_t K,
-                                                        int32_t rows_per_block, int want_bias) {
-    constexpr int NG = 32 * NGT, KG = 32 * KGT, TILES = NGT * KGT, TPW = (TILES + 3) / 4;
-    constexpr int ND = (32 * NG) / 256, NX = (32 * KG) / 256;
-    __shared__ float ds[32 * NG];
-    __shared__ float xs[32 * KG];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int32_t n_base = blockIdx.z * NG, k_base = blockIdx.y * KG;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = (r_begin + rows_per_block < M) ? r_begin + rows_per_block : M;
-    f32x16 acc[TPW];
-#pragma unroll
-    for (int j = 0; j < TPW; ++j) acc[j] = f32x16{0};
-    float bsum = 0.0f;
-    float dreg[ND], xreg[NX];
-    int fl[EMER_CHAIN_MAX_SEGS];
-#pragma unroll
-    for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) fl[s] = __ffs(sx.s[s].f > 0 ? sx.s[s].f : 1) - 1;
-    auto fetch = [&](int64_t r0) {
-        int64_t ray0[EMER_CHAIN_MAX_SEGS];
-        int32_t rem0[EMER_CHAIN_MAX_SEGS];
-#pragma unroll
-        for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) {  // per-ray operands: ONE scalar division per segment per 32-row tile
-            const int32_t rd = sx.s[s].row_div > 0 ? sx.s[s].row_div : 1;
-            ray0[s] = (rd == 1) ? r0 : r0 / rd;
-            rem0[s] = (int32_t)(r0 - ray0[s] * rd);
-        }
-#pragma unroll
-        for (int i = 0; i < ND; ++i) {
-            const int idx = tid + i * 256;
-            const int r = idx / NG, c = idx % NG;
-            const int64_t gr = r0 + r;
-            const int32_t gn = n_base + c;
-            dreg[i] = (gr < r_end && gn < N) ? ((sx.col0 && gn == 0) ? sx.col0[gr] : dpre[gr * ldd + gn]) : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const int idx = tid + i * 256;
-            const int r = idx / KG, c = idx % KG;
-            const int64_t gr = r0 + r;
-            const int32_t gk = k_base + c;
-            float v = 0.0f;
-            if (gr < r_end && gk < K) {
-#pragma unroll
-                for (int s = 0; s < EMER_CHAIN_MAX_SEGS; ++s) {
-                    if (s < sx.n && gk >= sx.s[s].col && gk < sx.s[s].col + sx.s[s].width) {
-                        const int32_t c = gk - sx.s[s].col;
-                        if (sx.s[s].mode == 1) {
-                            v = sx.s[s].ptr[((int64_t)(c >> fl[s]) * sx.s[s].n_total + gr) * sx.s[s].f + (c & (sx.s[s].f - 1))];
-                        } else if (sx.s[s].row_div == 1) {
-                            v = sx.s[s].ptr[gr * sx.s[s].ld + c];
-                        } else {  // per-ray operand (32 <= row_div in practice: at most one ray boundary inside a tile)
-                            const int32_t rem = rem0[s] + r;
-                            const int64_t ray = rem < sx.s[s].row_div ? ray0[s] : ray0[s] + rem / sx.s[s].row_div;
-                            v = sx.s[s].ptr[ray * sx.s[s].ld + c];
-                        }
-                    }
-                }
-            }
-            xreg[i] = v;
-        }
-    };
-    fetch(r_begin);
-    for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
-#pragma unroll
-        for (int i = 0; i < ND; ++i) ds[tid + i * 256] = dreg[i];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xs[tid + i * 256] = xreg[i];
-        __syncthreads();
-        if (r0 + 32 < r_end) fetch(r0 + 32);
-#pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-            const int t = wave + 4 * j;
-            if (t < TILES) {
-                const int nt = t / KGT, kt = t % KGT;
-                const float *ap = ds + (lane >> 5) * NG + nt * 32 + (lane & 31);
-                const float *bp = xs + (lane >> 5) * KG + kt * 32 + (lane & 31);
-#pragma unroll 4
-                for (int s = 0; s < 16; ++s)
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s * NG], bp[2 * s * KG], acc[j], 0, 0, 0);
-            }
-        }
-        if (want_bias && blockIdx.y == 0 && wave == 0 && lane < NG) {
-#pragma unroll 8
-            for (int r = 0; r < 32; ++r) bsum += ds[r * NG + lane];
-        }
-        __syncthreads();
-    }
-    float *__restrict__ part = partials + (int64_t)blockIdx.x * ((int64_t)N * K + N);
-#pragma unroll
-    for (int j = 0; j < TPW; ++j) {
-        const int t = wave + 4 * j;
-        if (t >= TILES) continue;
-        const int nt = t / KGT, kt = t % KGT;
-        const int32_t k = k_base + kt * 32 + (lane & 31);
-        if (k >= K) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int32_t n = n_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (n < N) part[(int64_t)n * K + k] = acc[j][r];
-        }
-    }
-    if (want_bias && blockIdx.y == 0 && wave == 0 && lane < NG && n_base + lane < N) part[(int64_t)N * K + n_base + lane] = bsum;
-}
-
 // Streaming dW on the bf16 matrix pipe with fp32-equivalent results [r3].
 // dW[n][k] = sum_m dPre[m][n] X[m][k] as v_mfma_f32_32x32x16_bf16: i = n, j = k, the reduction index is the ROW.  Lane
 // (j = lane & 31, kg = lane >> 5) supplies the eight rows m0 + 8 kg .. + 7 of ONE column of each operand: a load
@@ -808,22 +790,6 @@ template <int W> __device__ __forceinline__ void vec_load(const float *p, float 
     for (int i = 0; i < W; ++i) v[i] = f[i];
 }
 
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-// (a, b) -> packed bf16 pairs h, m, l with a = a_h + a_m + a_l (+ <= 2^-24 |a|); both subtractions are exact
-__device__ __forceinline__ void split3(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    h = pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-    l = pk_bf16(sa, sb);
-}
-#define EMER_MF32(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
 
 // VEC = false: tile t of an operand holds columns 32 t + j (one dword per tile per row).
 // VEC = true : tile t holds columns T j + t (T = tiles of that operand) -- the assignment of columns to MFMA tiles is
@@ -1112,12 +1078,11 @@ extern "C" int emer_wgrad_segmented(const float *dpre, int64_t ldd, const float 
     EMER_REQUIRE(dpre && segs && workspace && dw && n_segs >= 1 && n_segs <= EMER_CHAIN_MAX_SEGS, "wgrad_segmented: bad arguments");
     SegX sx;
     sx.n = n_segs; sx.col0 = col0;
-    DwDst ddst = dw_dst_identity(k);
-    ddst.n = n_segs; ddst.ld = ld_dw;
+    DwReduceJob job{0, n, k, dw, ld_dw, dbias, n_segs, {0}, {0}, {0}};   // segment s of the partial lands at its dst_col
     int32_t covered = 0;
     for (int s = 0; s < n_segs; ++s) {
         EMER_REQUIRE(segs[s].dst_col >= 0 && segs[s].dst_col + segs[s].width <= ld_dw, "wgrad_segmented: segment %d lands outside dw (ld_dw=%lld)", s, (long long)ld_dw);
-        ddst.col[s] = segs[s].col; ddst.width[s] = segs[s].width; ddst.dst[s] = segs[s].dst_col;
+        job.col[s] = segs[s].col; job.width[s] = segs[s].width; job.dst[s] = segs[s].dst_col;
         EMER_REQUIRE(segs[s].ptr && segs[s].col == covered && ((segs[s].mode == 0 && segs[s].row_div >= 1) || (segs[s].mode == 1 && segs[s].f >= 1)),
                      "wgrad_segmented: segments must be contiguous, mode 0 or 1");
         sx.s[s] = segs[s];
@@ -1126,10 +1091,8 @@ extern "C" int emer_wgrad_segmented(const float *dpre, int64_t ldd, const float 
     for (int s = n_segs; s < EMER_CHAIN_MAX_SEGS; ++s) sx.s[s] = segs[0];
     EMER_REQUIRE(covered == k, "wgrad_segmented: segments cover %d columns, k = %d", covered, k);
     hipStream_t st = as_stream(stream);
-    const int32_t NG = n <= 32 ? 32 : 64;
-    const int32_t KG = k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 128 : 256));
-    const int32_t rpb = dw_rows_per_block(m, n, k);
-    const int32_t n_row_blocks = (int32_t)ceil_div(m, rpb);
+    const DwPlan p = dw_plan(m, n, k);
+    const int64_t stride = (int64_t)n * k + n;
     bool stream_ok = n <= 64 && k <= 128;
     for (int s = 0; s < n_segs; ++s) stream_ok = stream_ok && (segs[s].mode == 1 || segs[s].row_div == 1);
     const int NT = n <= 32 ? 1 : 2;
@@ -1148,8 +1111,8 @@ extern "C" int emer_wgrad_segmented(const float *dpre, int64_t ldd, const float 
     // register file (hundreds of spilled registers); such shapes (no shipped head) take the LDS-staged kernel below
     if (NT * KT >= 8 && !full) stream_ok = false;
     if (stream_ok) {  // no per-ray operand: operands stream straight into the MFMA layout
-        const dim3 sgrid((uint32_t)n_row_blocks);
-#define EMER_WSK(A, B, V, C, F, BI) hipLaunchKernelGGL((wgrad_stream_kernel<A, B, V, C, F, BI>), sgrid, dim3(256), 0, st, dpre, ldd, sx, workspace, m, n, k, rpb, dbias ? 1 : 0)
+        const dim3 sgrid((uint32_t)p.n_row_blocks);
+#define EMER_WSK(A, B, V, C, F, BI) hipLaunchKernelGGL((wgrad_stream_kernel<A, B, V, C, F, BI>), sgrid, dim3(256), 0, st, dpre, ldd, sx, workspace, m, n, k, p.rpb, dbias ? 1 : 0)
 #define EMER_WSL(A, B, V, C, F) do { if (A * B >= 8 && !dbias) EMER_WSK(A, B, V, C, F, (A * B < 8)); else EMER_WSK(A, B, V, C, F, true); } while (0)
 #define EMER_WS(A, B) do { if (vec && col0 && full) EMER_WSL(A, B, true, true, true); else if (vec && col0) EMER_WSL(A, B, true, true, false); \
                            else if (vec && full) EMER_WSL(A, B, true, false, true); else if (vec) EMER_WSL(A, B, true, false, false); \
@@ -1162,19 +1125,9 @@ extern "C" int emer_wgrad_segmented(const float *dpre, int64_t ldd, const float 
 #undef EMER_WSL
 #undef EMER_WSK
         if (int rc = check_launch("wgrad_stream")) return rc;
-        const int64_t stride = (int64_t)n * k + n;
-        hipLaunchKernelGGL(linear_dw_reduce_kernel, dim3((uint32_t)ceil_div(stride, 256), dw_reduce_splits(n_row_blocks, stride)), dim3(256), 0, st,
-                           workspace, n_row_blocks, stride, (int64_t)n * k, dw, dbias, ddst);
-        return check_launch("wgrad_reduce");
+        return launch_dw_reduce_job(workspace, p.n_row_blocks, stride, job, "wgrad_reduce", st);
     }
-    const dim3 grid((uint32_t)n_row_blocks, (uint32_t)ceil_div(k, KG), (uint32_t)ceil_div(n, NG));
-#define EMER_WG(A, B) hipLaunchKernelGGL((wgrad_seg_kernel<A, B>), grid, dim3(256), 0, st, dpre, ldd, sx, workspace, m, n, k, rpb, dbias ? 1 : 0)
-    if (NG == 32) { if (KG == 32) EMER_WG(1, 1); else if (KG == 64) EMER_WG(1, 2); else if (KG == 128) EMER_WG(1, 4); else EMER_WG(1, 8); }
-    else          { if (KG == 32) EMER_WG(2, 1); else if (KG == 64) EMER_WG(2, 2); else if (KG == 128) EMER_WG(2, 4); else EMER_WG(2, 8); }
-#undef EMER_WG
+    EMER_DW_DISPATCH(wgrad_seg_kernel, p, st, dpre, ldd, sx, workspace, m, n, k, p.rpb, dbias ? 1 : 0);
     if (int rc = check_launch("wgrad_segmented")) return rc;
-    const int64_t stride = (int64_t)n * k + n;
-    hipLaunchKernelGGL(linear_dw_reduce_kernel, dim3((uint32_t)ceil_div(stride, 256), dw_reduce_splits(n_row_blocks, stride)), dim3(256), 0, st, workspace, n_row_blocks, stride,
-                       (int64_t)n * k, dw, dbias, ddst);
-    return check_launch("wgrad_reduce");
+    return launch_dw_reduce_job(workspace, p.n_row_blocks, stride, job, "wgrad_reduce", st);
 }

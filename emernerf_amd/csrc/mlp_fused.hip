@@ -37,10 +37,9 @@
 // to K = 64 / 128.  In the backward the kernel reduces dPre0 / dPre1 over the samples of each ray, which is all the
 // per-ray operands need (dhray, dW_h and the biases are tiny per-ray GEMMs on those sums).
 #include "common.h"
+#include "bf16x3.h"
 
 namespace emer {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kFThreads = 384;  // rgb head: 6 waves; two workgroups per CU = 3 waves per SIMD = 170 VGPRs each
 constexpr int kNThreads = 512;  // neck: 8 waves; two workgroups per CU = 4 waves per SIMD = 128 VGPRs each
@@ -52,24 +51,7 @@ struct WSrc {
     int32_t n, k;    // real extents (zero padded in LDS)
 };
 
-// ---- bf16x3 operands ---------------------------------------------------------------------------------------------
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-// (a, b) -> packed bf16 pairs h, m, l with a = a_h + a_m + a_l (+ <= 2^-24 |a|); both subtractions are exact
-__device__ __forceinline__ void split3(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    h = pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-    l = pk_bf16(sa, sb);
-}
-
+// ---- bf16x3 operands (the split and the MFMA macros: csrc/bf16x3.h) -------------------------------------------------
 // B operand (activations) of KS k-steps: lane (m, g) holds, for k-step s, features 32 s + 16 (j >> 2) + 4 g + (j & 3)
 template <int KS> struct Opd { u32x4 h[KS], m[KS], l[KS]; };
 
@@ -121,8 +103,6 @@ __device__ __forceinline__ W3 w3_tile(const W3 w, int p0) { return W3{w.p + p0 *
 __device__ __forceinline__ void stage_b(float *dst, int npad, const float *b, int n) {
     for (int i = threadIdx.x; i < npad; i += (int)blockDim.x) dst[i] = (b && i < n) ? b[i] : 0.0f;
 }
-
-#define EMER_MF(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
 
 // acc[p] (output tile p) += W[16p .. 16p+15][:] . in, fp32-equivalent (six bf16 partial products, smallest first).
 // Two output tiles are interleaved so that consecutive instructions hit different accumulators; the scheduling barrier
@@ -555,10 +535,8 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_bwd_kernel(const NeckBwdArg
 // The 16x16 tiles of dW (64 x 64 and 64 x K0: 24 tiles = 96 registers) stay in the wave's accumulators for the whole
 // launch -- two waves per SIMD instead of four; an LDS copy per workgroup with ds_add_f32 was tried first and is
 // hopeless on this chip (0.37 lane-adds per clock per CU, DESIGN 4.1: 2 ms for this kernel).  The waves of a workgroup are
-// summed through LDS once at the end and the per-workgroup partials by linear_dw_reduce_kernel.  dPre never goes to HBM
+// summed through LDS once at the end and the per-workgroup partials by linear_dw_reduce_multi_kernel.  dPre never goes to HBM
 // and h1 / enc / d are read once: the separate weight-gradient pass of the neck (two launches, 0.94 GB) is gone.
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using s16x4 = __attribute__((ext_vector_type(4))) short;
 struct SwT { u32x2 h, m, l; };  // one 16-row x 16-feature tile, rows on the reduction index, three bf16 terms
 
 struct SelE { unsigned a0, a1; };  // the two non-zero registers of the selection fragments (built once per lane)
@@ -580,7 +558,6 @@ __device__ __forceinline__ SwT to_rows(const Opd<KS> &o, int p, const SelE e, fl
     if (colsum) *colsum += ((tl[0] + tl[1]) + (tl[2] + tl[3])) + ((tm[0] + tm[1]) + (tm[2] + tm[3])) + ((th[0] + th[1]) + (th[2] + th[3]));
     return t;
 }
-#define EMER_MF16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, A), __builtin_bit_cast(s16x4, B), C, 0, 0, 0)
 // acc[p][b] (lane (j, g), register r: dW[16 p + 4 g + r][16 b + j]) += sum over the tile's rows of a[p][row][.] * bt[b][row][.]
 // Products outermost: consecutive instructions hit different accumulators.
 template <int NA, int NB>
@@ -593,8 +570,6 @@ __device__ __forceinline__ void dw_tiles(f32x4 (&acc)[NA][NB], const SwT (&a)[NA
 }
 
 struct SwP { u32x4 h, m, l; };  // eight reduction-index entries per lane and term: the operand of a K = 32 (16 x 16) or K = 16 (32 x 32) dW step
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-#define EMER_MF32(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
 // two 16-feature tiles (rows on the reduction index) -> the operand of their 32-feature block
 __device__ __forceinline__ SwP block32(const SwT &ta, const SwT &tb) {
     SwP o;

@@ -127,6 +127,8 @@ SIGNATURES = {
     "emer_ray_head_fwd": [_P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, c_int, _P, _P, _P, _P],
     "emer_ray_head_bwd": [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_int, _P, _P, _P, _P],
     "emer_ray_wgrad": [_P, c_int32, c_int64, _P],
+    "emer_ray_jobs": [_P, c_int32, _P],
+    "emer_dw_reduce_defer": [_P],
     "emer_sample_uniform": [_P, c_uint64, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P],
     "emer_lidar_sample_rays": [_P, c_uint64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "emer_sample_importance": [_P, c_int64, _P, c_uint64, c_int64, _P, _P, _P],

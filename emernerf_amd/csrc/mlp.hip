@@ -26,6 +26,7 @@
 //   mlp_chain         : up to EMER_CHAIN_MAX_LAYERS dense layers on 16-row tiles, one wave per tile, weights in LDS.
 #include "common.h"
 #include "bf16x3.h"
+#include "dw_reduce.h"
 
 #include <type_traits>
 
@@ -363,78 +364,21 @@ __global__ __launch_bounds__(256) void wgrad_seg_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ sum of the partials
-// dw[i] += sum_b partials[b][off + i]  (i < n*k),  dbias[i - n*k] += ...  (i >= n*k), for up to EMER_DW_MAX_JOBS (dW | dbias) pairs of
-// ONE partial buffer in one launch (blockIdx.z = job): the fused backward kernels leave two or three gradients in each workgroup's
-// partial, and three 5-us launches in a row cost more than the sums themselves.
-// The partial blocks are cut into gridDim.y ranges so that the (small) n*k + n extent still fills the chip; each
-// thread sums its range with four independent accumulators (loads in flight) and merges with one f32 atomic.
-struct DwDst {  // where column k of the (virtually concatenated) operand lands in dw: dw[n * ld + dst + (k - col)]
-    int32_t col[EMER_CHAIN_MAX_SEGS], width[EMER_CHAIN_MAX_SEGS], dst[EMER_CHAIN_MAX_SEGS];
-    int32_t n, K;
-    int64_t ld;
-};
-struct DwJobs {
-    int32_t n_jobs;
-    int64_t off[EMER_DW_MAX_JOBS], nk[EMER_DW_MAX_JOBS], extent[EMER_DW_MAX_JOBS];   // start inside a partial, floats of dW, floats of dW + dbias
-    float *dw[EMER_DW_MAX_JOBS], *dbias[EMER_DW_MAX_JOBS];
-    DwDst dst[EMER_DW_MAX_JOBS];
-};
+// up to EMER_DW_MAX_JOBS (dW | dbias) pairs of ONE partial buffer in one launch (blockIdx.z = job): the fused backward kernels leave
+// two or three gradients in each workgroup's partial, and three 5-us launches in a row cost more than the sums themselves.  The body
+// (dw_reduce_stage), its argument block and the split rule are in dw_reduce.h.
 __global__ __launch_bounds__(256) void linear_dw_reduce_multi_kernel(const float *__restrict__ partials, int32_t n_blocks, int64_t stride, const DwJobs jobs) {
-    const int j = (int)blockIdx.z;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= jobs.extent[j]) return;
-    const int32_t per = (n_blocks + (int32_t)gridDim.y - 1) / (int32_t)gridDim.y;
-    const int32_t b0 = (int32_t)blockIdx.y * per;
-    const int32_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
-    if (b0 >= b1) return;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    const float *__restrict__ p = partials + jobs.off[j] + i;
-    int32_t b = b0;
-    for (; b + 4 <= b1; b += 4) {
-        a0 += p[(int64_t)b * stride];
-        a1 += p[(int64_t)(b + 1) * stride];
-        a2 += p[(int64_t)(b + 2) * stride];
-        a3 += p[(int64_t)(b + 3) * stride];
-    }
-    for (; b < b1; ++b) a0 += p[(int64_t)b * stride];
-    const float a = (a0 + a1) + (a2 + a3);
-    const DwDst &dst = jobs.dst[j];
-    if (i < jobs.nk[j]) {
-        const int32_t n = (int32_t)(i / dst.K), k = (int32_t)(i - (int64_t)n * dst.K);
-        int64_t o = -1;
-#pragma unroll
-        for (int sg = 0; sg < EMER_CHAIN_MAX_SEGS; ++sg)
-            if (sg < dst.n && k >= dst.col[sg] && k < dst.col[sg] + dst.width[sg]) o = (int64_t)n * dst.ld + dst.dst[sg] + (k - dst.col[sg]);
-        if (o >= 0) __hip_atomic_fetch_add(jobs.dw[j] + o, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (jobs.dbias[j]) __hip_atomic_fetch_add(jobs.dbias[j] + (i - jobs.nk[j]), a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dw_reduce_stage(partials, n_blocks, stride, jobs, (int)blockIdx.z, (int64_t)blockIdx.x * 256 + threadIdx.x, (int32_t)blockIdx.y, (int32_t)gridDim.y);
 }
 
-static inline uint32_t dw_reduce_splits(int32_t n_blocks, int64_t stride) {
-    // ~2048 workgroups in total, at least 8 partial blocks per range
-    int64_t s = 2048 / ((stride + 255) / 256);
-    if (s > n_blocks / 8) s = n_blocks / 8;
-    return (uint32_t)(s < 1 ? 1 : s);
-}
+// emer_dw_reduce_defer: where the next multi-gradient reduction of this thread is described instead of launched (one-shot)
+static thread_local emer_dw_reduce_args *g_defer_reduce = nullptr;
 
 // The one launch of the reduction.  `span`: floats of a partial that the grid (and the split rule) is sized for; 0: the largest job.
 static int launch_reduce(const float *partials, int32_t n_blocks, int64_t stride, int n_jobs, const DwReduceJob *jb, int64_t span,
                          const char *what, hipStream_t st) {
     DwJobs jobs;
-    jobs.n_jobs = n_jobs;
-    int64_t max_extent = 0;
-    for (int j = 0; j < EMER_DW_MAX_JOBS; ++j) {
-        const bool on = j < n_jobs;
-        const DwReduceJob &q = jb[on ? j : 0];
-        DwDst &d = jobs.dst[j];   // n_segs == 0: one block, column c of the partial at dw[row * ld_dw + c]
-        for (int i = 0; i < EMER_CHAIN_MAX_SEGS; ++i) {
-            const bool seg = i < q.n_segs;
-            d.col[i] = seg ? q.col[i] : 0; d.width[i] = seg ? q.width[i] : (i == 0 && q.n_segs <= 0 ? q.k : 0); d.dst[i] = seg ? q.dst[i] : 0;
-        }
-        d.n = q.n_segs > 0 ? q.n_segs : 1; d.K = q.k; d.ld = q.ld_dw;
-        jobs.off[j] = q.off; jobs.nk[j] = (int64_t)q.n * q.k; jobs.extent[j] = on ? (int64_t)q.n * q.k + (q.db ? q.n : 0) : 0;
-        jobs.dw[j] = q.dw; jobs.dbias[j] = q.db;
-        if (jobs.extent[j] > max_extent) max_extent = jobs.extent[j];
-    }
+    const int64_t max_extent = dw_reduce_pack(n_jobs, jb, jobs);
     if (span <= 0) span = max_extent;
     hipLaunchKernelGGL(linear_dw_reduce_multi_kernel, dim3((uint32_t)ceil_div(span, 256), dw_reduce_splits(n_blocks, span), (uint32_t)n_jobs),
                        dim3(256), 0, st, partials, n_blocks, stride, jobs);
@@ -445,6 +389,16 @@ static int launch_reduce(const float *partials, int32_t n_blocks, int64_t stride
 // of every partial; `n_segs` == 0: dW goes to dw[row * ld + column]; else column block s = columns col[s] .. col[s] + width[s] - 1 lands
 // at dw[row * ld_dw + dst[s] ..].
 int launch_dw_reduce_multi(const float *partials, int32_t n_blocks, int64_t stride, int n_jobs, const DwReduceJob *jb, hipStream_t st) {
+    if (emer_dw_reduce_args *cap = g_defer_reduce) {   // deferred: the caller runs it as a job of emer_ray_jobs
+        g_defer_reduce = nullptr;
+        cap->partials = partials; cap->stride = stride; cap->n_blocks = n_blocks; cap->n_jobs = n_jobs;
+        for (int j = 0; j < n_jobs; ++j) {
+            emer_dw_reduce_job &o = cap->job[j];
+            o.off = jb[j].off; o.n = jb[j].n; o.k = jb[j].k; o.dw = jb[j].dw; o.ld_dw = jb[j].ld_dw; o.db = jb[j].db; o.n_segs = jb[j].n_segs; o.pad_ = 0;
+            for (int i = 0; i < 4; ++i) { o.col[i] = jb[j].col[i]; o.width[i] = jb[j].width[i]; o.dst[i] = jb[j].dst[i]; }
+        }
+        return EMER_OK;
+    }
     return launch_reduce(partials, n_blocks, stride, n_jobs, jb, 0, "dw_reduce_multi", st);
 }
 
@@ -519,6 +473,12 @@ static int launch_linear(const float *x, int64_t ldx, const float *w, int64_t sb
 }  // namespace emer
 
 using namespace emer;
+
+extern "C" int emer_dw_reduce_defer(emer_dw_reduce_args *capture) {
+    g_defer_reduce = capture;
+    return EMER_OK;
+}
+
 
 extern "C" int emer_linear_fwd(const float *x, int64_t ldx, const float *w, const float *bias, float *y, int64_t ldy,
                                int64_t m, int32_t n, int32_t k, int act, float *aux_density, void *stream) {

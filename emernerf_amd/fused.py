@@ -25,7 +25,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, ray_jobs
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP
 
 MAX_LAYERS, MAX_SEGS = 6, 3
@@ -351,6 +351,7 @@ _RIDERS: dict = {}   # data_ptr of a neck's geometry features -> the rider whose
 
 def clear_riders() -> None:
     _RIDERS.clear()
+    ray_jobs.clear_fronts()
 
 
 def _neck_fwd(enc: Tensor, W0, B0, W1, B1, n_out: int, want_h: bool):
@@ -441,14 +442,18 @@ def _field_fwd(enc: Tensor, W0, B0, W1, B1, rider: RgbRider):
     R, Kh = hr.shape
     geo = torch.empty((N, 64), device=dev, dtype=torch.float32)
     dens = torch.empty((N,), device=dev, dtype=torch.float32)
-    rb = torch.empty((R, 128), device=dev, dtype=torch.float32)
+    rb = ray_jobs.front_rb(rider.hray, rider.params[:4])   # already computed by the front launch on exactly these tensors?
+    parked = rb is not None
+    if not parked:
+        rb = torch.empty((R, 128), device=dev, dtype=torch.float32)
     rec = rgb_recompute(R, rider.S) if rider.keep else 0   # [r6] recomputing backward: the activations it recomputes are not stored
     a1 = torch.empty((N, 64), device=dev, dtype=torch.float32) if (rider.keep and rec != 1) else None
     a2 = torch.empty((N, 64), device=dev, dtype=torch.float32) if (rider.keep and rec == 0) else None
     out = torch.empty((N, 3), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.call("emer_ray_pre_fwd", _p(hr), hr.stride(0), R, Kh, 64, _p(RW0), RW0.stride(0), _p(RB0), _p(RW1[:, 64:]), RW1.stride(0),
-                  _p(RB1), _p(rb), 128, _stream(enc))
+        if not parked:
+            _lib.call("emer_ray_pre_fwd", _p(hr), hr.stride(0), R, Kh, 64, _p(RW0), RW0.stride(0), _p(RB0), _p(RW1[:, 64:]), RW1.stride(0),
+                      _p(RB1), _p(rb), 128, _stream(enc))
         _lib.call("emer_field_fwd", _p(enc), L, F, R, rider.S, _p(W0), _p(B0), _p(W1), _p(B1), _p(rb), _p(rb[:, 64:]), 128, Kh,
                   _p(RW0), _p(RW1), _p(RW2), _p(RB2), _p(geo), _p(dens), _p(a1), _p(a2), _p(out), _stream(enc))
     rider.geo_ptr, rider.a1, rider.a2, rider.out, rider.rb = geo.data_ptr(), a1, a2, out, rb
@@ -549,7 +554,7 @@ def density_mlp(enc_lm: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor) 
 # ------------------------------------------------------------------------------------------ rgb head
 class _RgbHeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hray: Tensor, geo: Tensor, S: int, w0, b0, w1, b1, w2, b2, pre: Optional[RgbRider] = None):
+    def forward(ctx, hray: Tensor, geo: Tensor, S: int, w0, b0, w1, b1, w2, b2, pre: Optional[RgbRider] = None, rb_front: Optional[Tensor] = None):
         ctx.set_materialize_grads(False)
         hr, W0, B0, W1, B1, W2, B2 = _c(hray), _c(w0), _c(b0), _c(w1), _c(b1), _c(w2), _c(b2)
         g = geo.detach()
@@ -579,10 +584,13 @@ class _RgbHeadFn(torch.autograd.Function):
         if ctx.fast:
             # per-ray part of layers 0 and 1 as per-ray pre-activations (ONE 8192-row launch instead of two 1M-row GEMMs),
             # reading the two column blocks of W0 / W1 in place
-            rb = torch.empty((R, 2 * H), device=dev, dtype=torch.float32)
-            with torch.cuda.device(dev):
-                _lib.call("emer_ray_pre_fwd", _p(hr), hr.stride(0), R, Kh, H, _p(W0), W0.stride(0), _p(B0), _p(W1[:, H:]), W1.stride(0),
-                          _p(B1), _p(rb), 2 * H, _stream(g))
+            if rb_front is not None and rb_front.shape == (R, 2 * H):
+                rb = rb_front   # the front launch evaluated it on exactly these tensors (rgb_head checked)
+            else:
+                rb = torch.empty((R, 2 * H), device=dev, dtype=torch.float32)
+                with torch.cuda.device(dev):
+                    _lib.call("emer_ray_pre_fwd", _p(hr), hr.stride(0), R, Kh, H, _p(W0), W0.stride(0), _p(B0), _p(W1[:, H:]), W1.stride(0),
+                              _p(B1), _p(rb), 2 * H, _stream(g))
             rb0, rb1 = rb[:, :H], rb[:, H:]
             with torch.cuda.device(dev):
                 _lib.call("emer_rgb_head_fwd", _p(g), g.stride(0), _p(rb0), _p(rb1), rb.stride(0), R, S, Kh, _p(W0), _p(W1), _p(W2), _p(B2),
@@ -605,7 +613,7 @@ class _RgbHeadFn(torch.autograd.Function):
     def backward(ctx, dout: Optional[Tensor]):
         hr, g, W0, W1, W2, a1, a2, out, rb = ctx.saved_tensors
         if dout is None:
-            return (None,) * 10
+            return (None,) * 11
         S = ctx.S
         N, NG = g.shape
         R, Kh = hr.shape
@@ -628,7 +636,13 @@ class _RgbHeadFn(torch.autograd.Function):
                 # [r4] the weight gradients of the per-sample column blocks of layers 0 / 1 (and layer 2) inside the backward kernel:
                 # dpre1 / dpre0 never reach memory and the two streamed weight-gradient launches are gone
                 ws = torch.empty((n_ws,), device=dev, dtype=torch.float32)
-                with torch.cuda.device(dev):
+                # the per-ray tail (reduction of the partials, hray's weight-gradient blocks, d hray) may wait for the step's two job
+                # launches (ray_jobs): only when hray is an output of _RayInputsFn of this forward (its backward flushes before it reads
+                # d hray; torch consumers of other rows would not), and only into .grad itself -- a fresh tensor is added to .grad as
+                # soon as this backward returns
+                defer = ray_jobs.may_defer(hr) and all(t is not None for t in ctx.sinks)
+                cap = ray_jobs.DwReduceArgs()
+                with torch.cuda.device(dev), (ray_jobs.capture_dw_reduce(cap) if defer else contextlib.nullcontext()):
                     if ctx.recompute:   # [r6] hidden activations recomputed from geo + the per-ray pre-activations
                         _lib.call("emer_rgb_head_bwd_recompute", _p(_c(dout)), _p(out), _p(a1), _p(g), g.stride(0), _p(rb), _p(rb[:, H:]), rb.stride(0), R, S, Kh,
                                   _p(W0), _p(W1), _p(W2), _p(dgeo), _p(s1), _p(s0), _p(ws), _p(tw0), tw0.stride(0), _p(tw1), tw1.stride(0), _p(tw2),
@@ -636,12 +650,20 @@ class _RgbHeadFn(torch.autograd.Function):
                     else:
                         _lib.call("emer_rgb_head_bwd_fused", _p(_c(dout)), _p(out), _p(a1), _p(a2), _p(g), g.stride(0), R, S, Kh, _p(W0), _p(W1), _p(W2),
                                   _p(dgeo), _p(s1), _p(s0), _p(ws), _p(tw0), tw0.stride(0), _p(tw1), tw1.stride(0), _p(tw2), tw2.stride(0), _p(tb2), _stream(g))
-                ray_wgrad([(s1, [(hr, Kh, H)], tw1, tb1), (s0, [(hr, Kh, 0)], tw0, tb0)], g)
+                wjobs = [(s1, [(hr, Kh, H)], tw1, tb1), (s0, [(hr, Kh, 0)], tw0, tb0)]
                 dhray = torch.empty((R, Kh), device=dev, dtype=torch.float32)
+                if defer:
+                    level_a = [ray_jobs.job(ray_jobs.PRE_BWD, ray_jobs.pre_bwd_args(s0, s1, Kh, W0, W1, dhray))]   # (the longer member first)
+                    if cap.n_jobs:
+                        level_a.append(ray_jobs.job(ray_jobs.DW_REDUCE, cap))
+                    ray_jobs.enqueue(level_a, [ray_jobs.wgrad_job(*j) for j in wjobs], (ws, s0, s1, hr, W0, W1, dhray, tw0, tb0, tw1, tb1, tw2, tb2), g,
+                                     outputs=[(dhray, hr)])
+                    return dhray, dgeo, None, rw0, rb0, rw1, rb1, rw2, rb2, None, None
+                ray_wgrad(wjobs, g)
                 with torch.cuda.device(dev):
                     _lib.call("emer_ray_pre_bwd", _p(s0), _p(s1), H, R, Kh, H, _p(W0), W0.stride(0), _p(W1[:, H:]), W1.stride(0), _p(dhray), Kh,
                               _stream(g))
-                return dhray, dgeo, None, rw0, rb0, rw1, rb1, rw2, rb2, None
+                return dhray, dgeo, None, rw0, rb0, rw1, rb1, rw2, rb2, None, None
             dpre2 = torch.empty((N, C), device=dev, dtype=torch.float32)
             dpre1 = torch.empty((N, H), device=dev, dtype=torch.float32)
             dpre0 = torch.empty((N, H), device=dev, dtype=torch.float32)
@@ -664,7 +686,7 @@ class _RgbHeadFn(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.call("emer_ray_pre_bwd", _p(s0), _p(s1), H, R, Kh, H, _p(W0), W0.stride(0), _p(W1[:, H:]), W1.stride(0), _p(dhray), Kh,
                           _stream(g))
-            return dhray, dgeo, None, rw0, rb0, rw1, rb1, rw2, rb2, None
+            return dhray, dgeo, None, rw0, rb0, rw1, rb1, rw2, rb2, None, None
         dpre2 = (_c(dout) * out * (1.0 - out)).contiguous()            # sigmoid'
         dpre1 = torch.empty((N, H), device=dev, dtype=torch.float32)
         dpre0 = torch.empty((N, H), device=dev, dtype=torch.float32)
@@ -683,7 +705,7 @@ class _RgbHeadFn(torch.autograd.Function):
         dw1, db1 = wgrad(dpre1, [seg(a1, 0, H), seg(hr, H, Kh, row_div=S), seg(g, H + Kh, NG, ld=g.stride(0))], H + K0)
         dw0, db0 = wgrad(dpre0, [seg(hr, 0, Kh, row_div=S), seg(g, Kh, NG, ld=g.stride(0))], K0)
         dhray = dh.view(R, S, Kh).sum(dim=1)
-        return dhray, dgeo, None, dw0, db0, dw1, db1, dw2, db2, None
+        return dhray, dgeo, None, dw0, db0, dw1, db1, dw2, db2, None, None
 
 
 def rgb_head(hray: Tensor, geo: Tensor, samples_per_ray: int, w0, b0, w1, b1, w2, b2) -> Tensor:
@@ -694,7 +716,8 @@ def rgb_head(hray: Tensor, geo: Tensor, samples_per_ray: int, w0, b0, w1, b1, w2
                 and geo.dim() == 2 and geo.shape[1] == 64 and geo.stride(0) == 64
                 and all(a is b for a, b in zip(pre.params, (w0, b0, w1, b1, w2, b2))))
         pre = pre if same else None
-    return _RgbHeadFn.apply(*_ng(hray, geo, samples_per_ray, w0, b0, w1, b1, w2, b2), pre)
+    rb_front = ray_jobs.front_rb(hray, (w0, b0, w1, b1)) if pre is None else None
+    return _RgbHeadFn.apply(*_ng(hray, geo, samples_per_ray, w0, b0, w1, b1, w2, b2), pre, rb_front)
 
 
 # ------------------------------------------------------------------------------------------ per-ray inputs
@@ -705,7 +728,7 @@ class _RayInputsFn(torch.autograd.Function):
     a zero fill and an atomic index_add)."""
 
     @staticmethod
-    def forward(ctx, weight: Tensor, idx: Tensor, dirs: Tensor, max_deg: int):
+    def forward(ctx, weight: Tensor, idx: Tensor, dirs: Tensor, max_deg: int, front=None):
         ctx.set_materialize_grads(False)
         w = _c(weight)
         assert idx.dtype == torch.int64 and idx.dim() == 1 and dirs.dim() == 2 and dirs.dtype == torch.float32 and dirs.stride(1) == 1
@@ -715,38 +738,96 @@ class _RayInputsFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             out_rgb = torch.empty((R, P + E), device=dev, dtype=torch.float32)
             out_sky = torch.empty((R, P + E), device=dev, dtype=torch.float32)
-            _lib.call("emer_ray_inputs_fwd", _p(dirs), dirs.stride(0), _p(idx), idx.stride(0), _p(w), w.shape[0], E, max_deg, R,
-                      _p(out_rgb), P + E, _p(out_sky), P + E, _stream(dirs))
+            if not (ray_jobs.ENABLED and front is not None and _front_launch(front, w, idx, dirs, max_deg, out_rgb, out_sky)):
+                _lib.call("emer_ray_inputs_fwd", _p(dirs), dirs.stride(0), _p(idx), idx.stride(0), _p(w), w.shape[0], E, max_deg, R,
+                          _p(out_rgb), P + E, _p(out_sky), P + E, _stream(dirs))
         ctx.save_for_backward(idx)
         ctx.sink, ctx.shape, ctx.P = _sink(weight), tuple(w.shape), P
+        ctx.out_ptrs = (out_rgb.data_ptr(), out_sky.data_ptr())
+        ray_jobs.register_rows(out_rgb, out_sky)   # the only inputs whose gradient a head may defer: it comes back to THIS node
         return out_rgb, out_sky
 
     @staticmethod
     def backward(ctx, g_rgb: Optional[Tensor], g_sky: Optional[Tensor]):
         if g_rgb is None and g_sky is None:
-            return None, None, None, None
+            return None, None, None, None, None
         (idx,) = ctx.saved_tensors
         dev = idx.device
         P = ctx.P
+        # a head's backward that deferred its per-ray jobs handed back the tensor those jobs will WRITE: legal only if that very
+        # tensor arrives here (one consumer per input; a second one would have made autograd add unwritten memory on the way)
+        ray_jobs.check_single_consumer(ctx.out_ptrs[0], g_rgb)
+        ray_jobs.check_single_consumer(ctx.out_ptrs[1], g_sky)
 
         def cols(g):
             if g is None:
                 return None, 0
-            g = g if (g.dtype == torch.float32 and g.stride(1) == 1) else g.to(torch.float32).contiguous()
+            if not (g.dtype == torch.float32 and g.stride(1) == 1):
+                ray_jobs.flush()   # (a converted copy must see the written gradient)
+                g = g.to(torch.float32).contiguous()
             return g[:, P:], g.stride(0)
 
         (ga, lda), (gb, ldb) = cols(g_rgb), cols(g_sky)
         tw, rw = _target(ctx.sink, ctx.shape, dev)
+        if ray_jobs.armed():
+            # launch A (what the heads queued: their row-local chains, the reduction) and launch B (their weight gradients and this
+            # table's gradient, which reads the input gradients launch A writes)
+            ray_jobs.flush([ray_jobs.job(ray_jobs.EMBED_GRAD, ray_jobs.embed_grad_args(ga, lda, gb, ldb, idx, ctx.shape[0], ctx.shape[1], tw))], idx)
+            return rw, None, None, None, None
         with torch.cuda.device(dev):
             _lib.call("emer_embed_grad", _p(ga), lda, _p(gb), ldb, _p(idx), idx.stride(0), idx.shape[0], ctx.shape[0], ctx.shape[1],
                       _p(tw), _stream(idx))
-        return rw, None, None, None
+        return rw, None, None, None, None
 
 
+def _plain(p) -> bool:
+    return isinstance(p, Tensor) and p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
 
-def ray_inputs(emb_weight: Tensor, idx: Tensor, dirs: Tensor, max_deg: int):
-    """(rgb-head rows, sky-head rows), each [R, PE + emb_dim], for per-ray directions [R, 3] and embedding indices [R]."""
-    return _RayInputsFn.apply(*_ng(emb_weight, idx, dirs, max_deg))
+
+def _front_launch(front, w: Tensor, idx: Tensor, dirs: Tensor, max_deg: int, out_rgb: Tensor, out_sky: Tensor) -> bool:
+    """The FRONT launch (ray_jobs): both heads' input rows and, in the same launch and the same workgroups, what each head computes
+    from its rows alone -- the rgb head's per-ray pre-activations, the whole sky head.  front = (rgb head's (w0 .. b2) | None,
+    sky head's (w0 .. b2) | None, the sky head's final activation).  The results are parked for _field_fwd / rgb_head / skip_mlp3,
+    which take them only for the very same input and parameters; False: nothing to fuse (the caller launches the plain kernel)."""
+    rgb_p, sky_p, sky_act = front
+    R, K = out_rgb.shape
+    fits = lambda p: p is not None and len(p) == 6 and all(_plain(t) for t in p) and K <= 64 and p[0].shape[0] == 64 and p[2].shape[0] == 64
+    rgb_ok = fits(rgb_p) and rgb_p[0].shape[1] >= K and rgb_p[2].shape[1] >= 64 + K
+    sky_ok = (fits(sky_p) and sky_p[0].shape == (64, K) and sky_p[2].shape == (64, 64 + K) and sky_p[4].shape[1] == 64
+              and sky_p[4].shape[0] <= 16 and sky_act in (ACT_NONE, ACT_SIGMOID))
+    if not (rgb_ok or sky_ok) or R == 0:
+        return False
+    dev = out_rgb.device
+    parked = ray_jobs.Front()
+    jobs = []
+    if sky_ok:   # the longer chain first
+        W0, B0, W1, B1, W2, B2 = (p.detach() for p in sky_p)
+        C = W2.shape[0]
+        rb = torch.empty((R, 128), device=dev, dtype=torch.float32)
+        a1 = torch.empty((R, 64), device=dev, dtype=torch.float32)
+        a2 = torch.empty((R, 64), device=dev, dtype=torch.float32)
+        out = torch.empty((R, C), device=dev, dtype=torch.float32)
+        jobs.append(ray_jobs.fwd_chain_job(ray_jobs.inputs_args(dirs, idx, w, max_deg, None, out_sky), ray_jobs.pre_fwd_args(out_sky, W0, B0, W1, B1, rb),
+                                           ray_jobs.head_fwd_args(rb, W1, W2, B2, sky_act, a1, a2, out)))
+        parked.sky = (out_sky, tuple(sky_p), tuple(p._version for p in sky_p), sky_act, (rb, a1, a2, out))
+    else:
+        jobs.append(ray_jobs.job(ray_jobs.INPUTS, ray_jobs.inputs_args(dirs, idx, w, max_deg, None, out_sky)))
+    if rgb_ok:
+        W0, B0, W1, B1 = (p.detach() for p in rgb_p[:4])
+        rb = torch.empty((R, 128), device=dev, dtype=torch.float32)
+        jobs.append(ray_jobs.fwd_chain_job(ray_jobs.inputs_args(dirs, idx, w, max_deg, out_rgb, None), ray_jobs.pre_fwd_args(out_rgb, W0, B0, W1, B1, rb)))
+        parked.rgb = (out_rgb, tuple(rgb_p[:4]), tuple(p._version for p in rgb_p[:4]), rb)
+    else:
+        jobs.append(ray_jobs.job(ray_jobs.INPUTS, ray_jobs.inputs_args(dirs, idx, w, max_deg, out_rgb, None)))
+    ray_jobs.launch(jobs, dirs)
+    ray_jobs.park(out_rgb, out_sky, parked)
+    return True
+
+
+def ray_inputs(emb_weight: Tensor, idx: Tensor, dirs: Tensor, max_deg: int, front=None):
+    """(rgb-head rows, sky-head rows), each [R, PE + emb_dim], for per-ray directions [R, 3] and embedding indices [R].
+    ``front``: the heads that will consume the rows (see _front_launch), to evaluate their per-ray stages in the same launch."""
+    return _RayInputsFn.apply(*_ng(emb_weight, idx, dirs, max_deg), front)
 
 
 # ------------------------------------------------------------------------- 3-layer skip MLP on row-major input
@@ -756,17 +837,25 @@ class _SkipMLP3Fn(torch.autograd.Function):
     instead of three Linear launches each way with [rows, 64] round trips."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, w0, b0, w1, b1, w2, b2, final_act: int):
+    def forward(ctx, x: Tensor, w0, b0, w1, b1, w2, b2, final_act: int, front=None):
         ctx.set_materialize_grads(False)
         X, W0, B0, W1, B1, W2, B2 = _c(x), _c(w0), _c(b0), _c(w1), _c(b1), _c(w2), _c(b2)
         N, K0 = X.shape
         H, C = W0.shape[0], W2.shape[0]
         assert W0.shape[1] == K0 and W1.shape[1] == H + K0 and W2.shape[1] == H and H % 4 == 0
         dev = X.device
+        ctx.fast = H == 64 and K0 <= 64 and C <= 16
+        if front is not None and ctx.fast and X.data_ptr() == x.data_ptr():
+            # already evaluated by the front launch on exactly these tensors (skip_mlp3 checked): nothing to launch
+            _, a1, a2, out = front
+            assert a1.shape == (N, H) and a2.shape == (N, H) and out.shape == (N, C)
+            ctx.save_for_backward(X, W0, W1, W2, a1, a2, out)
+            ctx.final_act = final_act
+            ctx.sinks = tuple(_sink(p) for p in (w0, b0, w1, b1, w2, b2))
+            return out.view_as(out)   # (a fresh tensor object for autograd; the parked one stays as it is)
         a1 = torch.empty((N, H), device=dev, dtype=torch.float32)
         a2 = torch.empty((N, H), device=dev, dtype=torch.float32)
         out = torch.empty((N, C), device=dev, dtype=torch.float32)
-        ctx.fast = H == 64 and K0 <= 64 and C <= 16
         if ctx.fast:
             # a few thousand rows: two small launches (the input's share of layers 0 and 1, then the rest of the MLP)
             # instead of the general chain kernel, whose set-up dominates at this size
@@ -793,7 +882,7 @@ class _SkipMLP3Fn(torch.autograd.Function):
     def backward(ctx, dout: Optional[Tensor]):
         X, W0, W1, W2, a1, a2, out = ctx.saved_tensors
         if dout is None:
-            return (None,) * 8
+            return (None,) * 9
         N, K0 = X.shape
         H, C = W0.shape[0], W2.shape[0]
         dev = X.device
@@ -801,8 +890,25 @@ class _SkipMLP3Fn(torch.autograd.Function):
         dpre1 = torch.empty((N, H), device=dev, dtype=torch.float32)
         dpre0 = torch.empty((N, H), device=dev, dtype=torch.float32)
         dx = torch.empty((N, K0), device=dev, dtype=torch.float32)
+        sw0, sb0, sw1, sb1, sw2, sb2 = ctx.sinks
+        tw2, rw2 = _target(sw2, (C, H), dev)
+        tb2, rb2 = _target(sb2, (C,), dev)
+        tw1, rw1 = _target(sw1, (H, H + K0), dev)
+        tb1, rb1 = _target(sb1, (H,), dev)
+        tw0, rw0 = _target(sw0, (H, K0), dev)
+        tb0, rb0 = _target(sb0, (H,), dev)
+        per_ray = ctx.fast and N <= 65536   # per-ray head: all three layers' weight gradients in one launch
         if ctx.fast:
             dpre2 = torch.empty((N, C), device=dev, dtype=torch.float32)
+            wjobs = [(dpre2, [(a2, H, 0)], tw2, tb2), (dpre1, [(a1, H, 0), (X, K0, H)], tw1, tb1), (dpre0, [(X, K0, 0)], tw0, tb0)]
+            if per_ray and ray_jobs.may_defer(X) and all(t is not None for t in ctx.sinks):
+                # the whole backward waits for the step's two job launches (ray_jobs): the row-local chain in the first, the weight
+                # gradients in the second (only into .grad itself: a fresh tensor is added to .grad as soon as this backward returns)
+                chain = ray_jobs.bwd_chain_job(ray_jobs.head_bwd_args(d, out, a1, a2, W1, W2, ctx.final_act, dpre2, dpre1, dpre0),
+                                               ray_jobs.pre_bwd_args(dpre0, dpre1, K0, W0, W1, dx))
+                ray_jobs.enqueue([chain], [ray_jobs.wgrad_job(*j) for j in wjobs],
+                                 (d, out, a1, a2, X, W0, W1, W2, dpre2, dpre1, dpre0, dx, tw0, tb0, tw1, tb1, tw2, tb2), X, outputs=[(dx, X)])
+                return dx, rw0, rb0, rw1, rb1, rw2, rb2, None, None
             with torch.cuda.device(dev):
                 _lib.call("emer_ray_head_bwd", _p(d), _p(out), _p(a1), _p(a2), N, _p(W1), W1.stride(0), _p(W2), C, ctx.final_act, _p(dpre2),
                           _p(dpre1), _p(dpre0), _stream(X))
@@ -818,26 +924,20 @@ class _SkipMLP3Fn(torch.autograd.Function):
                        layer(W1, None, c1, cx + H, transposed=True, n_slice=(H, H + K0)),
                        layer(W0, None, cx, cx + H, transposed=True, accumulate=True, store=dx)],
                       cx + H + _r4(K0), N, X)
-        sw0, sb0, sw1, sb1, sw2, sb2 = ctx.sinks
-        tw2, rw2 = _target(sw2, (C, H), dev)
-        tb2, rb2 = _target(sb2, (C,), dev)
-        tw1, rw1 = _target(sw1, (H, H + K0), dev)
-        tb1, rb1 = _target(sb1, (H,), dev)
-        tw0, rw0 = _target(sw0, (H, K0), dev)
-        tb0, rb0 = _target(sb0, (H,), dev)
-        if ctx.fast and N <= 65536:  # per-ray head: all three layers in one launch
-            ray_wgrad([(dpre2, [(a2, H, 0)], tw2, tb2), (dpre1, [(a1, H, 0), (X, K0, H)], tw1, tb1), (dpre0, [(X, K0, 0)], tw0, tb0)], X)
+        if per_ray:
+            ray_wgrad(wjobs, X)
         else:
             wgrad(dpre2, [seg(a2, 0, H)], H, out_w=tw2, out_b=tb2)
             wgrad(dpre1, [seg(a1, 0, H), seg(X, H, K0)], H + K0, out_w=tw1, out_b=tb1)
             wgrad(dpre0, [seg(X, 0, K0)], K0, out_w=tw0, out_b=tb0)
-        return dx, rw0, rb0, rw1, rb1, rw2, rb2, None
+        return dx, rw0, rb0, rw1, rb1, rw2, rb2, None, None
 
 
 def skip_mlp3(x: Tensor, w0, b0, w1, b1, w2, b2, final_act: int = ACT_SIGMOID) -> Tensor:
     """final_act(MLP3-skip1(x)) for x [rows, K0]; final_act ACT_SIGMOID or ACT_NONE."""
     assert final_act in (ACT_SIGMOID, ACT_NONE)
-    return _SkipMLP3Fn.apply(*_ng(x, w0, b0, w1, b1, w2, b2, final_act))
+    front = ray_jobs.front_sky(x, (w0, b0, w1, b1, w2, b2), final_act)
+    return _SkipMLP3Fn.apply(*_ng(x, w0, b0, w1, b1, w2, b2, final_act), front)
 
 
 # ----------------------------------------------------------------- plain nn.Sequential heads (shadow / flow / dino)

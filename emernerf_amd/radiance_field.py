@@ -579,8 +579,19 @@ class RadianceField(nn.Module):
         hit = _EMBED_CACHE.get(ck)
         if hit is None:
             _EMBED_CACHE.clear()
-            hit = _EMBED_CACHE[ck] = fused.ray_inputs(w, idx, d, enc.max_deg)
+            hit = _EMBED_CACHE[ck] = fused.ray_inputs(w, idx, d, enc.max_deg, front=self._front_heads())
         return hit
+
+    def _front_heads(self):
+        """The two per-ray heads that consume the rows of _ray_inputs, for fused.ray_inputs to evaluate their per-ray stages in
+        its own launch: ((w0 .. b2) of the rgb head | None, (w0 .. b2) of the sky head | None, the sky head's final activation).
+        Only the 3-layer, skip-at-1, 64-wide heads that the per-ray kernels cover; the heads check again what they pick up."""
+        def params(head):
+            if head is None or not (len(head.layers) == 3 and list(head.skip_connections) == [1] and head.hidden_dims == 64):
+                return None
+            lw = tuple(p for l in head.layers for p in (l.weight, l.bias))
+            return None if any(p is None for p in lw) else lw
+        return params(self.rgb_head), params(getattr(self, "sky_head", None)), fused.ACT_SIGMOID
 
     def _query_rgb_fused(self, directions, geo_feats, dynamic_geo_feats, data_dict):
         """Fused rgb head: per-ray [dir-PE | appearance emb] stays per ray, geo stays per sample, the whole

@@ -27,7 +27,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import Tensor
 
-from . import fused, ops
+from . import fused, ops, ray_jobs
 from .prop_net import PropNetEstimator, get_proposal_requires_grad_fn
 from .radiance_field import DensityField, RadianceField, build_density_field, build_radiance_field_from_cfg
 from .render_utils import render_rays
@@ -590,17 +590,35 @@ class Trainer:
     def _forward_backward(self, data: Dict[str, Tensor], prop_grad: bool) -> Tensor:
         """zero grads -> render -> losses -> backward (everything of a step that is the same from step to step)."""
         self.flat.zero_grad()
-        with fused.grad_sinks(True):
+        # the heads' per-ray backward jobs wait in a queue for two launches (ray_jobs): flushed where their input gradients meet
+        # (fused._RayInputsFn.backward) and, for a step whose embedding takes no gradient, after each backward() below
+        with fused.grad_sinks(True), ray_jobs.deferred_tail(self._ray_tail_ok()):
             results = render_rays(radiance_field=self.model, proposal_estimator=self.estimator, proposal_networks=self.props,
                                   data_dict=data, cfg=self.rcfg, proposal_requires_grad=prop_grad)
             if prop_grad:
                 prop_loss = self.estimator.compute_loss(results["extras"]["trans"], loss_scaler=self.loss_scale)
                 prop_loss.backward(gradient=self._seed(prop_loss))
+                ray_jobs.flush()
                 self._launch_prop_bucket()
             target, loss = self._scaled_losses(results, data)
             target.backward(gradient=self._seed(target))
+            ray_jobs.flush()   # before anything reads a gradient (normally a no-op)
         fused.join_side_stream()  # weight gradients written on the side stream are complete from here on
         return loss
+
+    def _ray_tail_ok(self) -> bool:
+        """Whether the queue for the heads' per-ray backward jobs is ARMED this step (ray_jobs.deferred_tail); a head then defers only
+        if its rows are outputs of fused._RayInputsFn of this forward (ray_jobs.may_defer).  A deferred input gradient is
+        written after the head's backward has returned it, so it must go straight to the producer of the per-ray rows: the model
+        has ONE rgb head and ONE sky head on those rows (the static kind; with a dynamic field the rows feed two rgb heads and
+        autograd would add their gradients first).  Data-parallel steps launch gradient buckets from inside the backward, which
+        a deferred job could write into afterwards: the tail is off there."""
+        if self._dp_on or not ray_jobs.ENABLED:
+            return False
+        m = self.model
+        single = m.dynamic_xyz_encoder is None and getattr(m, "flow_xyz_encoder", None) is None and not getattr(m, "enable_feature_head", False)
+        assert not single or self.kind == "static", "the per-ray rows of this model have more than one consumer per head"
+        return single
 
     def _graphed_forward_backward(self, data: Dict[str, Tensor], prop_grad: bool) -> Tensor:
         """hipGraph replay of _forward_backward: one graph per step type (with / without proposal-net training),

@@ -698,6 +698,83 @@ typedef struct emer_ray_wgrad_job {
 } emer_ray_wgrad_job;
 int emer_ray_wgrad(const emer_ray_wgrad_job *jobs, int32_t n_jobs, int64_t m, void *stream);
 
+/* Several per-ray stages in ONE launch: the jobs of one emer_ray_jobs launch run side by side.  The jobs of one launch must not
+ * depend on one another (nothing orders workgroups of different jobs).  Measured at 8192 rays: members that use
+ * few CUs overlap (two emer_ray_wgrad launches and emer_embed_grad, 62 us, are 27 us as one launch); the row-local stages are one
+ * full workgroup per CU each and gain little: 1 to 9 us per launch in two sessions, against sums of 37 and 43 us.
+ * A job is the argument list of one of the entry points above (same meaning, same checks, same results bit for bit), or a
+ * CHAIN of row-local stages that a 32-row workgroup runs back to back on its own rows:
+ *   FWD_CHAIN  emer_ray_inputs_fwd -> emer_ray_pre_fwd [-> emer_ray_head_fwd]   (n_stages 2 or 3)
+ *   BWD_CHAIN  emer_ray_head_bwd -> emer_ray_pre_bwd
+ * Every stage of a chain still writes its outputs to memory exactly as the separate launch does; the caller wires the stages up
+ * through the pointers (e.g. pre.h == in.out_sky, head.rb == pre.rb), all stages of a chain share the row count.
+ * DW_REDUCE is the reduction of a fused backward kernel's per-workgroup partials, as captured by emer_dw_reduce_defer. */
+#define EMER_RAY_JOBS_MAX 8
+#define EMER_RAY_JOB_INPUTS 1
+#define EMER_RAY_JOB_PRE_FWD 2
+#define EMER_RAY_JOB_HEAD_FWD 3
+#define EMER_RAY_JOB_HEAD_BWD 4
+#define EMER_RAY_JOB_PRE_BWD 5
+#define EMER_RAY_JOB_WGRAD 6
+#define EMER_RAY_JOB_EMBED_GRAD 7
+#define EMER_RAY_JOB_DW_REDUCE 8
+#define EMER_RAY_JOB_FWD_CHAIN 9
+#define EMER_RAY_JOB_BWD_CHAIN 10
+typedef struct emer_ray_inputs_args {
+    const float *dirs; int64_t ld_dirs; const int64_t *idx; int64_t idx_stride; const float *emb;
+    int32_t n_emb, emb_dim, max_deg, pad_; int64_t n_rays; float *out_rgb; int64_t ld_rgb; float *out_sky; int64_t ld_sky;
+} emer_ray_inputs_args;
+typedef struct emer_ray_pre_fwd_args {
+    const float *h; int64_t ld_h, n_rays; int32_t kh, n_hidden; const float *wa; int64_t ld_wa; const float *ba, *wb; int64_t ld_wb;
+    const float *bb; float *rb; int64_t ld_rb;
+} emer_ray_pre_fwd_args;
+typedef struct emer_ray_pre_bwd_args {
+    const float *s0, *s1; int64_t ld_s, n_rays; int32_t kh, n_hidden; const float *wa; int64_t ld_wa; const float *wb; int64_t ld_wb;
+    float *dh; int64_t ld_dh;
+} emer_ray_pre_bwd_args;
+typedef struct emer_ray_head_fwd_args {
+    const float *rb; int64_t ld_rb, n_rows; const float *w1; int64_t ld_w1; const float *w2, *b2; int32_t n_out, act;
+    float *a1, *a2, *out;
+} emer_ray_head_fwd_args;
+typedef struct emer_ray_head_bwd_args {
+    const float *dout, *out, *a1, *a2; int64_t n_rows; const float *w1; int64_t ld_w1; const float *w2; int32_t n_out, act;
+    float *dpre2, *dpre1, *dpre0;
+} emer_ray_head_bwd_args;
+typedef struct emer_embed_grad_args {
+    const float *g_a; int64_t ld_a; const float *g_b; int64_t ld_b; const int64_t *idx; int64_t idx_stride, n_rays;
+    int32_t n_emb, emb_dim; float *dw;
+} emer_embed_grad_args;
+typedef struct emer_ray_wgrad_args { emer_ray_wgrad_job job; int64_t m; } emer_ray_wgrad_args;
+/* up to three (dW | dbias) gradients of one buffer of per-workgroup partials: gradient j is dW [n][k] (+ dbias [n] when db is set)
+ * at float `off` of each of the n_blocks partials (`stride` floats apart); n_segs == 0: dW goes to dw[row * ld_dw + column], else
+ * its column block s = columns col[s] .. col[s] + width[s] - 1 lands at dw[row * ld_dw + dst[s] ..] */
+typedef struct emer_dw_reduce_job {
+    int64_t off; int32_t n, k; float *dw; int64_t ld_dw; float *db; int32_t n_segs; int32_t col[4], width[4], dst[4]; int32_t pad_;
+} emer_dw_reduce_job;
+typedef struct emer_dw_reduce_args {
+    const float *partials; int64_t stride; int32_t n_blocks, n_jobs; emer_dw_reduce_job job[3];
+} emer_dw_reduce_args;
+typedef struct emer_ray_job {
+    int32_t kind, n_stages; /* n_stages: FWD_CHAIN only */
+    union {
+        emer_ray_inputs_args inputs;
+        emer_ray_pre_fwd_args pre_fwd;
+        emer_ray_head_fwd_args head_fwd;
+        emer_ray_head_bwd_args head_bwd;
+        emer_ray_pre_bwd_args pre_bwd;
+        emer_ray_wgrad_args wgrad;
+        emer_embed_grad_args embed_grad;
+        emer_dw_reduce_args dw_reduce;
+        struct { emer_ray_inputs_args in; emer_ray_pre_fwd_args pre; emer_ray_head_fwd_args head; } fwd_chain;
+        struct { emer_ray_head_bwd_args head; emer_ray_pre_bwd_args pre; } bwd_chain;
+    } u;
+} emer_ray_job;
+int emer_ray_jobs(const emer_ray_job *jobs, int32_t n_jobs, void *stream);
+/* One-shot: the NEXT multi-gradient reduction of per-workgroup partials that an entry point of this thread would launch
+ * (emer_rgb_head_bwd_fused / _recompute, emer_neck_bwd_fused, emer_rmlp_bwd_fused, ...) is not launched but described in *capture,
+ * for the caller to run later as an EMER_RAY_JOB_DW_REDUCE job (the partials must stay alive until then).  NULL disarms. */
+int emer_dw_reduce_defer(emer_dw_reduce_args *capture);
+
 /* ------------------------------------------------------------------------------------------------
  * Training-ray generation (replaces datasets/base/pixel_source.py:39-76 get_rays and
  * :564-731 sample_uniform_rays / sample_important_rays / the gathers of get_train_rays) on device-resident

@@ -694,3 +694,57 @@ def reg_partial_bound(name: str, n: int, stride: int) -> float:
     sums held to the squares' own size: 3 each, the sum 1, slack 1)."""
     own = {"dyn": 0.0, "shadow": 0.0, "feat": 3.0, "cycle": 8.0}[name]
     return float(-(-n // stride) + 6 + 4 + 3 + 3) + own
+
+
+# ------------------------------------------------------------------------------------------- per-ray head kernels
+# csrc/rayinputs.hip on arbitrary fp32 inputs: fp32 fmaf chains, the fp32-input MFMA and float atomics, held per entry to
+# c u abs_sum with abs_sum = sum |a| |b| + |bias| + |preloaded target| (every rounding sees a partial sum of at most that).
+# One rounding per addition, as for the MLP heads above; c counts the additions a term can pass through, slack 1 each.
+# tests/test_ray_exact_gpu.py holds the same kernels bit for bit on grid operands; these bounds hold random data entry by
+# entry, small entries included.  Worst err / bound on an MI355X (test_ray_pre_matches_fp64, test_ray_wgrad_matches_fp64 and
+# test_ray_inputs_and_embedding_gradient of tests/test_kernels_gpu.py at their shapes): ray_pre_fwd 0.28 (R = 70, Kh = 7), ray_pre_bwd
+# 0.098, ray_wgrad 0.022 (M = 1; 0.003 at M = 8192), embed_grad 0.042 (R = 8192, n_emb = 150); torch's fp32 evaluation on the CPU:
+# 0.34, 0.055, 0.046, 0.018 (tests/test_ray_bounds_cpu.py).
+
+
+def c_ray_pre_fwd(kh: int) -> float:
+    """ray_pre_fwd: per output an fmaf chain over k = 0 .. kh-1 that starts from the bias: kh roundings; slack 1."""
+    return float(kh + 1)
+
+
+def c_ray_pre_bwd(n_hidden: int) -> float:
+    """ray_pre_bwd: an fmaf chain over the 2 H columns of [s0 | s1] from zero: 2 H roundings; slack 1."""
+    return float(2 * n_hidden + 1)
+
+
+def c_ray_wgrad(m: int) -> float:
+    """ray_wgrad: a wave accumulates 64 rows of a 256-row chunk (2 rounds x 8 MFMA steps x 4 rows; one rounding per row
+    counted, however the instruction rounds its four products inside) = 64; the three quarter folds, of which a term passes
+    through at most two (2 + 0 / 3 + 1, then 0 + 1) = 2; one float atomic per chunk onto the target, each seeing the whole
+    partial = ceil(m / 256), the target's own value included in abs_sum; slack 1."""
+    return float(64 + 2 + -(-m // 256) + 1)
+
+
+def c_embed_grad(n_rays: int) -> float:
+    """embed_grad: a lane adds list entries two at a time, (ga + gb) + (ga' + gb') then acc += : 3 roundings for a term's own
+    iteration and one for each later iteration of at most 4 per scan round of 8192 rays (512 list slots / 128 per iteration)
+    = 4 ceil(R / 8192) + 2; six butterfly steps 6; the fixed-order sum over sixteen waves 16; the add onto the target 1;
+    slack 1."""
+    return float(4 * -(-n_rays // 8192) + 2 + 6 + 16 + 1 + 1)
+
+
+# The one constant that is not derived is the device sinf's error in the sin columns of the direction rows (emer_dir_encode,
+# emer_ray_inputs_fwd: sinf(x 2^k) and sinf(fl(x 2^k + half_pi_f32))).  Measured on an MI355X through emer_dir_encode itself
+# (remap off, max_deg = 1: the twelve sin columns of a row are sinf of a, 2 a, fl(a + hp), fl(2 a + hp) for its three
+# components) on the 38 348 616 arguments that tests/_ray_probe.sinf_sweep(21) yields -- |arg| up to 2053.6, twice what
+# max_deg = 10 forms from |x| <= 1, both signs: 2^21 uniform in [-1026, 1026], 2^21 uniform in [-2, 2], 2^20 log-spaced
+# magnitudes from 2^-40, the +-1600 fp32 neighbours of every zero crossing k pi and every eighth neighbour of every extremum
+# up to 326 pi, the 2^-10 grid times 2^k, 2^21 of x 2^k for uniform x -- against float64 sin of the fp32 argument: at most
+# 1.572 ulp of the result (at 1061.6062; 14.9 % of the results are not the correctly rounded one; by |arg|: 1.05 ulp below 2,
+# 1.44 in [2, 8), 1.52 in [8, 64), 1.55 in [64, 300), 1.57 beyond).  The error IS result-relative at the zero crossings: 1.18
+# ulp of the result over the 159 739 arguments within 1e-3 of a crossing k pi, k != 0 (results down to 2^-20), 0.48 ulp for
+# results in [2^-40, 2^-20), exact below (sinf(x) = x) and sinf(0) = 0: the argument reduction keeps enough bits of pi, so NO
+# absolute term is added.  E_SINF is the smallest power of two that is at least 1.5 x the measured maximum (1.5 x 1.572 =
+# 2.36 -> 4).  tests/test_ray_exact_gpu.py::test_device_sinf_error_is_inside_E_SINF runs sinf_sweep(17) in the suite.
+E_SINF_MEASURED = 1.572  # ulps
+E_SINF = 4.0

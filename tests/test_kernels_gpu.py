@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests import _composite_probe as CP
-from tests._bounds import assert_bound, c_atomic, c_forward, c_input_grad, c_sliced
+from tests._bounds import assert_bound, c_atomic, c_embed_grad, c_forward, c_input_grad, c_ray_pre_bwd, c_ray_pre_fwd, c_ray_wgrad, c_sliced
 
 pytestmark = pytest.mark.gpu
 
@@ -1102,7 +1102,8 @@ def test_nonfinite_gradient_is_reported_before_the_scatter(hip_lib, oracle, monk
 def test_ray_inputs_and_embedding_gradient(hip_lib, R, n_emb, E, max_deg):
     """emer_ray_inputs_fwd == [emer_dir_encode | weight[idx]] bit for bit (rgb rows on remapped directions, sky rows on raw
     ones); emer_embed_grad == index_add of the two consumers' gradients in fp64 (tolerance 1e-6 relative to the largest
-    entry: fp32 sums of up to R terms), and is deterministic (two runs bit-identical)."""
+    entry: fp32 sums of up to R terms) and per entry within c_embed_grad(R) u sum |g| (tests/_bounds.py), and is deterministic
+    (two runs bit-identical).  Bit for bit on exact probes: tests/test_ray_exact_gpu.py."""
     from emernerf_amd import fused, ops
     dev = _dev()
     g = torch.Generator().manual_seed(R + n_emb)
@@ -1121,11 +1122,15 @@ def test_ray_inputs_and_embedding_gradient(hip_lib, R, n_emb, E, max_deg):
     ref = torch.zeros(n_emb, E, dtype=torch.float64, device=dev).index_add_(0, idx, (ga[:, P:] + gb[:, P:]).double())
     (dw,) = torch.autograd.grad([rgb_rows, sky_rows], [w], [ga, gb], retain_graph=True)
     assert (dw.double() - ref).abs().max().item() <= 1e-6 * max(1.0, ref.abs().max().item())
+    mag = torch.zeros(n_emb, E, dtype=torch.float64, device=dev).index_add_(0, idx, ga[:, P:].abs().double() + gb[:, P:].abs().double())
+    assert_bound(dw.cpu().numpy(), ref.cpu().numpy(), mag.cpu().numpy(), c_embed_grad(R), f"embed_grad R={R} n_emb={n_emb} E={E}")
     (dw2,) = torch.autograd.grad([rgb_rows, sky_rows], [w], [ga, gb], retain_graph=True)
     assert torch.equal(dw, dw2)
     (dw_one,) = torch.autograd.grad([sky_rows], [w], [gb])  # one consumer only (eval of the sky head alone)
     ref_one = torch.zeros(n_emb, E, dtype=torch.float64, device=dev).index_add_(0, idx, gb[:, P:].double())
     assert (dw_one.double() - ref_one).abs().max().item() <= 1e-6 * max(1.0, ref_one.abs().max().item())
+    mag_one = torch.zeros(n_emb, E, dtype=torch.float64, device=dev).index_add_(0, idx, gb[:, P:].abs().double())
+    assert_bound(dw_one.cpu().numpy(), ref_one.cpu().numpy(), mag_one.cpu().numpy(), c_embed_grad(R), f"embed_grad (one consumer) R={R} n_emb={n_emb} E={E}")
 
 
 def test_ray_inputs_out_of_range_index_poisons_the_row(hip_lib):
@@ -1142,7 +1147,8 @@ def test_ray_inputs_out_of_range_index_poisons_the_row(hip_lib):
 @pytest.mark.parametrize("R,Kh,H", [(8192, 49, 64), (45, 33, 64), (1000, 64, 64), (70, 7, 16)])
 def test_ray_pre_matches_fp64(hip_lib, R, Kh, H):
     """emer_ray_pre_fwd / bwd against fp64 matmuls on the same column blocks of wider weight matrices (1e-6 relative to the
-    largest entry: fp32 dot products of <= 128 terms)."""
+    largest entry: fp32 dot products of <= 128 terms; per entry within c_ray_pre_fwd(Kh) / c_ray_pre_bwd(H) u (sum |w| |h| +
+    |bias|), tests/_bounds.py).  Bit for bit on exact probes: tests/test_ray_exact_gpu.py."""
     import ctypes
     from emernerf_amd import _lib
     dev = _dev()
@@ -1159,18 +1165,23 @@ def test_ray_pre_matches_fp64(hip_lib, R, Kh, H):
               b1.data_ptr(), rb.data_ptr(), 2 * H, st)
     ref = torch.cat([h.double() @ W0[:, :Kh].double().T + b0.double(), h.double() @ W1[:, H:H + Kh].double().T + b1.double()], 1)
     assert (rb.double() - ref).abs().max().item() <= 1e-6 * ref.abs().max().item()
+    mag = torch.cat([h.abs().double() @ W0[:, :Kh].abs().double().T + b0.abs().double(), h.abs().double() @ W1[:, H:H + Kh].abs().double().T + b1.abs().double()], 1)
+    assert_bound(rb.cpu().numpy(), ref.cpu().numpy(), mag.cpu().numpy(), c_ray_pre_fwd(Kh), f"ray_pre_fwd R={R} Kh={Kh} H={H}")
     s0, s1 = torch.randn(R, H, generator=g).to(dev), torch.randn(R, H, generator=g).to(dev)
     dh = torch.empty(R, Kh, device=dev)
     _lib.call("emer_ray_pre_bwd", s0.data_ptr(), s1.data_ptr(), H, R, Kh, H, W0.data_ptr(), W0.stride(0), wb.data_ptr(), W1.stride(0),
               dh.data_ptr(), Kh, st)
     ref = s0.double() @ W0[:, :Kh].double() + s1.double() @ W1[:, H:H + Kh].double()
     assert (dh.double() - ref).abs().max().item() <= 1e-6 * ref.abs().max().item()
+    mag = s0.abs().double() @ W0[:, :Kh].abs().double() + s1.abs().double() @ W1[:, H:H + Kh].abs().double()
+    assert_bound(dh.cpu().numpy(), ref.cpu().numpy(), mag.cpu().numpy(), c_ray_pre_bwd(H), f"ray_pre_bwd R={R} Kh={Kh} H={H}")
 
 
 @pytest.mark.parametrize("M", [8192, 300, 1])
 def test_ray_wgrad_matches_fp64(hip_lib, M):
     """emer_ray_wgrad: several per-ray layers' weight / bias gradients in one launch, accumulated into column blocks of wider
-    matrices, against fp64 (2e-6 relative to the largest entry: fp32 sums over <= 8192 rows in chunk order)."""
+    matrices, against fp64 (2e-6 relative to the largest entry: fp32 sums over <= 8192 rows in chunk order; per entry within
+    c_ray_wgrad(M) u (sum |dy| |x| + |target|), tests/_bounds.py).  Bit for bit on exact probes: tests/test_ray_exact_gpu.py."""
     from emernerf_amd import fused
     dev = _dev()
     g = torch.Generator().manual_seed(M)
@@ -1183,17 +1194,24 @@ def test_ray_wgrad_matches_fp64(hip_lib, M):
     db2, db1 = torch.ones(C, device=dev), torch.ones(H, device=dev)
     fused.ray_wgrad([(d2, [(a2, H, 0)], dw2, db2), (d1, [(a1, H, 0), (xs, K0, H + 10)], dw1, db1), (d0, [(x, K0, 0)], dw0, None)], x)
 
-    def chk(got, want):
+    def chk(got, want, mag, what):
         assert (got.double() - want).abs().max().item() <= 2e-6 * max(1.0, want.abs().max().item())
+        # per entry: c u (sum |dy| |x| + the preloaded 1); an untouched column (mag = the preloaded 1 alone) stays within its ulp
+        assert_bound(got.cpu().numpy(), want.cpu().numpy(), mag.cpu().numpy(), c_ray_wgrad(M), f"ray_wgrad {what} M={M}")
 
-    chk(dw2, 1.0 + d2.double().T @ a2.double())
-    chk(db2, 1.0 + d2.double().sum(0))
+    ab = lambda t: t.abs().double()
+    chk(dw2, 1.0 + d2.double().T @ a2.double(), 1.0 + ab(d2).T @ ab(a2), "dW2")
+    chk(db2, 1.0 + d2.double().sum(0), 1.0 + ab(d2).sum(0), "db2")
     want1 = torch.ones(H, H + K0 + 10, dtype=torch.float64, device=dev)
     want1[:, :H] += d1.double().T @ a1.double()
     want1[:, H + 10:] += d1.double().T @ xs.double()
-    chk(dw1, want1)  # columns H .. H+10 untouched
-    chk(db1, 1.0 + d1.double().sum(0))
-    chk(dw0, 1.0 + d0.double().T @ x.double())
+    mag1 = torch.ones(H, H + K0 + 10, dtype=torch.float64, device=dev)
+    mag1[:, :H] += ab(d1).T @ ab(a1)
+    mag1[:, H + 10:] += ab(d1).T @ ab(xs)
+    chk(dw1, want1, mag1, "dW1")  # columns H .. H+10 untouched
+    assert bool((dw1[:, H:H + 10] == 1.0).all()), "columns between the blocks must stay as they were"
+    chk(db1, 1.0 + d1.double().sum(0), 1.0 + ab(d1).sum(0), "db1")
+    chk(dw0, 1.0 + d0.double().T @ x.double(), 1.0 + ab(d0).T @ ab(x), "dW0")
 
 
 @pytest.mark.parametrize("N,C", [(1000, 64), (3, 4), (4096, 64)])

@@ -1,5 +1,5 @@
 """emer_ray_jobs (csrc/rayinputs.hip): the per-ray stages of the colour heads as members of one launch, against the stand-alone
-entry points -- the trusted side, held to the oracle by test_fused_gpu.py / test_kernels_gpu.py.  A member must compute what its
+entry points -- the trusted side, held bit for bit to fp64 by test_ray_exact_gpu.py and per entry by test_kernels_gpu.py.  A member must compute what its
 own launch computes BIT FOR BIT (same stage function, same per-lane work); the exceptions are the two stages that leave with
 relaxed float atomics from more than one workgroup per target, where neither side is reproducible:
 

@@ -15,13 +15,104 @@
 // dyadic accumulate / blend inputs), and inside a derived first-order bound on realistic rays (tests/_bounds.py:
 // render_bounds, dsigma_bound, epilogue_bounds, blend_c).  tests/_composite_model.py is a numpy model of the chunking,
 // carries, tail masking, median latch, four-wave split and quads below; tests/test_composite_bounds_cpu.py runs it and its
-// mutants against the same probes.  A change to the summation structure here needs the same change in that model.
+// mutants against the same probes.  Each stage that two kernels share (scan chunk, ray statistics, chunk_base pre-pass, reverse
+// chunk, blend ratios, the epilogue of ray_epilogue.h) is one function here, and the model follows those functions: a change to
+// the summation structure of one of them needs the same change in that model.  tools/composite_digests.py: bitwise A/B of a refactor.
 #include "common.h"
+#include "ray_epilogue.h"
 
 namespace emer {
 
 constexpr int kRaysPerBlockC = 4;
 
+// ---------------------------------------------------------------------------- stages shared by the scan kernels
+// One 64-sample chunk of ray r at samples base .. base + 63, lane = sample, in two steps: load_chunk, the loads with the tail mask
+// (a lane past S holds zeros), and scan_chunk, the wave scan of sigma*dt on top of `prefix` (the sum over the earlier chunks), T and
+// e = exp(-sigma*dt).  A kernel with more to load per sample issues it between the two, ahead of the scan's waits.  The forward
+// kernels carry `prefix` along, the backward kernels read it from chunk_base.
+struct ScanChunk {
+    int64_t i;  // flat (r, s)
+    bool ok;    // s < S
+    float sg, mid, dt, sdt, incl, T, e;
+};
+__device__ __forceinline__ ScanChunk load_chunk(const float *__restrict__ ts, const float *__restrict__ te,
+                                                const float *__restrict__ sigma, int64_t r, int32_t S, int32_t base, int lane) {
+    ScanChunk k;
+    const int32_t s = base + lane;
+    k.ok = s < S;
+    k.i = r * S + s;
+    const float a = k.ok ? ts[k.i] : 0.0f, b = k.ok ? te[k.i] : 0.0f;
+    k.sg = k.ok ? sigma[k.i] : 0.0f;
+    k.mid = (a + b) / 2.0f;
+    k.dt = b - a;
+    k.sdt = k.sg * k.dt;
+    return k;
+}
+__device__ __forceinline__ float sub_unfused(float x, float y) {
+#pragma clang fp contract(off)
+    return x - y;
+}
+__device__ __forceinline__ void scan_chunk(ScanChunk &k, int lane, float prefix, bool fused_excl) {
+    k.incl = wave_inclusive_sum(k.sdt, lane);
+    // exclusive = inclusive - own.  The compiler's contraction has always made ONE fused multiply-add of `incl - sg * dt` in the two
+    // forward kernels (the product unrounded) and left the rounded product and a subtraction in the two backward kernels; both are
+    // written out here, so that no kernel's T depends on what gets contracted around it (making the two agree is a numerical change)
+    const float own = fused_excl ? __fmaf_rn(-k.sg, k.dt, k.incl) : sub_unfused(k.incl, k.sdt);
+    k.T = expf(-(prefix + own));
+    k.e = expf(-k.sdt);
+}
+
+// (sum w, sum w*mid, median depth) of a ray, chunk by chunk.  Median depth: the midpoint of the first sample whose inclusive
+// cumsum(w) reaches 0.5, else of the last sample (render_utils.py:107-115).
+struct RayStats {
+    float wsum = 0.0f, wmid = 0.0f, wcarry = 0.0f, median = 0.0f, last_mid = 0.0f;
+    bool found = false;
+    __device__ __forceinline__ void step(float w, float mid, bool ok, int32_t base, int32_t S, int lane) {
+        const float cw = wcarry + wave_inclusive_sum(w, lane);
+        const unsigned long long hit = __ballot(ok && cw >= 0.5f);
+        if (!found && hit) {
+            const int first = __ffsll((long long)hit) - 1;
+            median = __shfl(mid, first, kWave);
+            found = true;
+        }
+        const int last_lane = (S - 1 - base) < (kWave - 1) ? (S - 1 - base) : (kWave - 1);
+        last_mid = __shfl(mid, last_lane, kWave);
+        wcarry = __shfl(cw, kWave - 1, kWave);
+        wsum += w;
+        wmid += w * mid;
+    }
+    __device__ __forceinline__ float4 finish() { return make_float4(wave_sum(wsum), wave_sum(wmid), found ? median : last_mid, 0.0f); }
+};
+
+// Pre-pass of the backward kernels: row[c] = sum of sigma*dt over the chunks before c (S <= 4096: at most 64 chunks).
+__device__ __forceinline__ void fill_chunk_base(const float *__restrict__ ts, const float *__restrict__ te,
+                                                const float *__restrict__ sigma, int64_t r, int32_t S, int lane, float *row) {
+    float carry = 0.0f;
+    for (int32_t c = 0; c < (S + kWave - 1) / kWave; ++c) {
+        const int32_t s = c * kWave + lane;
+        const int64_t i = r * S + s;
+        const float sdt = s < S ? sigma[i] * (te[i] - ts[i]) : 0.0f;
+        if (lane == 0) row[c] = carry;
+        carry += wave_sum(sdt);
+    }
+}
+
+// Reverse mode.  With a_i = sigma_i*dt_i, T_i = exp(-sum_{j<i} a_j), w_i = T_i (1 - exp(-a_i)):
+//   dL/da_i = gw_i * T_{i+1} - sum_{k>i} (gw_k w_k + gT_k T_k) + galpha_i * exp(-a_i),   T_{i+1} = T_i exp(-a_i)
+// with gw_i = d_weights_i + g(sum w) + g(sum w*mid) * mid_i (alpha_i = 1 - exp(-a_i) is a differentiable output too:
+// the reference's render_utils.py:73-77 forms weights = trans * alphas itself).
+// One chunk of it: the first two terms of dL/da_i (the caller adds its alpha term and multiplies by dt); `suffix`, the sum over
+// the later chunks of (gw w + gT T), moves on by this chunk.
+__device__ __forceinline__ float reverse_chunk(const ScanChunk &k, float gw, float gT, int lane, float &suffix) {
+    const float w = k.T * (1.0f - k.e);
+    const float term = k.ok ? gw * w + gT * k.T : 0.0f;
+    const float sfx_incl = wave_inclusive_suffix_sum(term, lane);
+    const float later = suffix + (sfx_incl - term);  // strictly-later samples
+    suffix += __shfl(sfx_incl, 0, kWave);
+    return gw * k.T * k.e - later;
+}
+
+// ---------------------------------------------------------------------------- weights / transmittance scan
 __global__ __launch_bounds__(256) void render_weights_fwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                                  const float *__restrict__ sigma, int64_t R, int32_t S,
                                                                  float *__restrict__ weights, float *__restrict__ trans,
@@ -31,63 +122,31 @@ __global__ __launch_bounds__(256) void render_weights_fwd_kernel(const float *__
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kRaysPerBlockC + wave;
     if (r >= R) return;
-    float carry = 0.0f;          // sum of sigma*dt over previous chunks
-    float wsum = 0.0f, wmid = 0.0f, wcarry = 0.0f;
-    float median = 0.0f;
-    bool found = false;
-    float last_mid = 0.0f;
+    float carry = 0.0f;  // sum of sigma*dt over previous chunks
+    RayStats stats;
     for (int32_t base = 0; base < S; base += kWave) {
-        const int32_t s = base + lane;
-        const bool ok = s < S;
-        const int64_t i = r * S + s;
-        const float a = ok ? ts[i] : 0.0f, b = ok ? te[i] : 0.0f, sg = ok ? sigma[i] : 0.0f;
-        const float sdt = sg * (b - a);
-        const float incl = wave_inclusive_sum(sdt, lane);
-        const float excl = carry + (incl - sdt);
-        const float T = expf(-excl);
-        const float al = 1.0f - expf(-sdt);
-        const float w = ok ? T * al : 0.0f;
-        if (ok) {
-            if (weights) weights[i] = w;
-            if (trans) trans[i] = T;
-            if (alphas) alphas[i] = al;
-            if (cdfs) cdfs[r * (int64_t)(S + 1) + s] = 1.0f - T;
-            if (t_mid) t_mid[i] = (a + b) / 2.0f;  // extras["t_vals"], extras["t_dist"] of rendering (render_utils.py:84-85)
-            if (t_dist) t_dist[i] = b - a;
+        ScanChunk k = load_chunk(ts, te, sigma, r, S, base, lane);
+        scan_chunk(k, lane, carry, true);
+        const float al = 1.0f - k.e;
+        const float w = k.ok ? k.T * al : 0.0f;
+        if (k.ok) {
+            if (weights) weights[k.i] = w;
+            if (trans) trans[k.i] = k.T;
+            if (alphas) alphas[k.i] = al;
+            if (cdfs) cdfs[r * (int64_t)(S + 1) + base + lane] = 1.0f - k.T;
+            if (t_mid) t_mid[k.i] = k.mid;  // extras["t_vals"], extras["t_dist"] of rendering (render_utils.py:84-85)
+            if (t_dist) t_dist[k.i] = k.dt;
         }
-        carry += __shfl(incl, kWave - 1, kWave);
-        if (ray_stats) {
-            const float mid = (a + b) / 2.0f;
-            // median depth: first sample whose inclusive cumsum(w) reaches 0.5 (render_utils.py:107-115)
-            const float cw = wcarry + wave_inclusive_sum(w, lane);
-            const unsigned long long hit = __ballot(ok && cw >= 0.5f);
-            if (!found && hit) {
-                const int first = __ffsll((long long)hit) - 1;
-                median = __shfl(mid, first, kWave);
-                found = true;
-            }
-            const int last_lane = (S - 1 - base) < (kWave - 1) ? (S - 1 - base) : (kWave - 1);
-            last_mid = __shfl(mid, last_lane, kWave);
-            wcarry = __shfl(cw, kWave - 1, kWave);
-            wsum += w;
-            wmid += w * mid;
-        }
+        carry += __shfl(k.incl, kWave - 1, kWave);
+        if (ray_stats) stats.step(w, k.mid, k.ok, base, S, lane);
     }
     if (cdfs && lane == 0) cdfs[r * (int64_t)(S + 1) + S] = 1.0f;  // 1 - [T, 0]
     if (ray_stats) {
-        wsum = wave_sum(wsum);
-        wmid = wave_sum(wmid);
-        if (lane == 0) {
-            float4 st = make_float4(wsum, wmid, found ? median : last_mid, 0.0f);
-            *reinterpret_cast<float4 *>(ray_stats + r * 4) = st;
-        }
+        const float4 st = stats.finish();
+        if (lane == 0) *reinterpret_cast<float4 *>(ray_stats + r * 4) = st;
     }
 }
 
-// Reverse mode.  With a_i = sigma_i*dt_i, T_i = exp(-sum_{j<i} a_j), w_i = T_i (1 - exp(-a_i)):
-//   dL/da_i = gw_i * T_{i+1} - sum_{k>i} (gw_k w_k + gT_k T_k) + galpha_i * exp(-a_i),   T_{i+1} = T_i exp(-a_i)
-// with gw_i = d_weights_i + g(sum w) + g(sum w*mid) * mid_i (alpha_i = 1 - exp(-a_i) is a differentiable output too:
-// the reference's render_utils.py:73-77 forms weights = trans * alphas itself).
 __global__ __launch_bounds__(256) void render_weights_bwd_kernel(const float *__restrict__ ts, const float *__restrict__ te,
                                                                  const float *__restrict__ sigma,
                                                                  const float *__restrict__ d_weights,
@@ -99,43 +158,21 @@ __global__ __launch_bounds__(256) void render_weights_bwd_kernel(const float *__
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kRaysPerBlockC + wave;
     const bool active = r < R;
-    const int32_t n_chunks = (S + kWave - 1) / kWave;
-    if (active) {
-        float carry = 0.0f;
-        for (int32_t c = 0; c < n_chunks; ++c) {
-            const int32_t s = c * kWave + lane;
-            const int64_t i = r * S + s;
-            const float sdt = s < S ? sigma[i] * (te[i] - ts[i]) : 0.0f;
-            if (lane == 0) chunk_base[wave][c] = carry;
-            carry += wave_sum(sdt);
-        }
-    }
+    if (active) fill_chunk_base(ts, te, sigma, r, S, lane, chunk_base[wave]);
     __syncthreads();
     if (!active) return;
     const float g0 = d_ray_stats ? d_ray_stats[r * 4 + 0] : 0.0f;  // [R,4] like ray_stats (columns 2, 3 carry no gradient)
     const float g1 = d_ray_stats ? d_ray_stats[r * 4 + 1] : 0.0f;
-    float suffix = 0.0f;  // sum over later chunks of (gw w + gT T)
-    for (int32_t c = n_chunks - 1; c >= 0; --c) {
-        const int32_t s = c * kWave + lane;
-        const bool ok = s < S;
-        const int64_t i = r * S + s;
-        const float a = ok ? ts[i] : 0.0f, b = ok ? te[i] : 0.0f, sg = ok ? sigma[i] : 0.0f;
-        const float dt = b - a;
-        const float sdt = sg * dt;
-        const float incl = wave_inclusive_sum(sdt, lane);
-        const float excl = chunk_base[wave][c] + (incl - sdt);
-        const float T = expf(-excl);
-        const float e = expf(-sdt);
-        const float w = T * (1.0f - e);
-        float gw = (ok && d_weights) ? d_weights[i] : 0.0f;
-        gw += g0 + g1 * ((a + b) / 2.0f);
-        const float gT = (ok && d_trans) ? d_trans[i] : 0.0f;
-        const float gA = (ok && d_alphas) ? d_alphas[i] : 0.0f;
-        const float term = ok ? gw * w + gT * T : 0.0f;
-        const float sfx_incl = wave_inclusive_suffix_sum(term, lane);
-        const float later = suffix + (sfx_incl - term);  // strictly-later samples
-        if (ok) d_sigma[i] = dt * (gw * T * e - later + gA * e);
-        suffix += __shfl(sfx_incl, 0, kWave);
+    float suffix = 0.0f;
+    for (int32_t c = (S + kWave - 1) / kWave - 1; c >= 0; --c) {
+        ScanChunk k = load_chunk(ts, te, sigma, r, S, c * kWave, lane);
+        scan_chunk(k, lane, chunk_base[wave][c], false);
+        float gw = (k.ok && d_weights) ? d_weights[k.i] : 0.0f;
+        gw += g0 + g1 * k.mid;
+        const float gT = (k.ok && d_trans) ? d_trans[k.i] : 0.0f;
+        const float gA = (k.ok && d_alphas) ? d_alphas[k.i] : 0.0f;
+        const float da = reverse_chunk(k, gw, gT, lane, suffix);
+        if (k.ok) d_sigma[k.i] = k.dt * (da + gA * k.e);
     }
 }
 
@@ -239,6 +276,12 @@ __global__ __launch_bounds__(256) void accumulate_bwd_wide_kernel(const float *_
 //   acc_rgb[r] = sum_s w * rgb,   acc_shadow[r] = sum_s w * shadow^2                  (:165-168,175)
 // The reference materialises a, b and the blended [R,S,3] colour (plus their autograd graph: ~30 elementwise
 // launches on 12 MB tensors); here one wave owns a ray, lanes walk its samples.
+struct BlendRatios { float inv, a, b; };
+__device__ __forceinline__ BlendRatios blend_ratios(float sig, float sig_s, float sig_d) {
+    const float inv = 1.0f / (sig + 1e-6f);
+    return {inv, sig_s * inv, sig_d * inv};
+}
+
 __global__ __launch_bounds__(256) void blend_accumulate_fwd_kernel(const float *__restrict__ w, const float *__restrict__ sig,
                                                                    const float *__restrict__ sig_s, const float *__restrict__ sig_d,
                                                                    const float *__restrict__ rgb_s, const float *__restrict__ rgb_d,
@@ -250,13 +293,13 @@ __global__ __launch_bounds__(256) void blend_accumulate_fwd_kernel(const float *
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, cs = 0.0f;
     for (int32_t s = lane; s < S; s += kWave) {
         const int64_t i = r * S + s;
-        const float wi = w[i], inv = 1.0f / (sig[i] + 1e-6f);
-        const float a = sig_s[i] * inv, b = sig_d[i] * inv;
+        const float wi = w[i];
+        const BlendRatios q = blend_ratios(sig[i], sig_s[i], sig_d[i]);
         const float sh = shadow ? shadow[i] : 0.0f;
-        const float ka = a * (1.0f - sh);
-        c0 += wi * (ka * rgb_s[i * 3 + 0] + b * rgb_d[i * 3 + 0]);
-        c1 += wi * (ka * rgb_s[i * 3 + 1] + b * rgb_d[i * 3 + 1]);
-        c2 += wi * (ka * rgb_s[i * 3 + 2] + b * rgb_d[i * 3 + 2]);
+        const float ka = q.a * (1.0f - sh);
+        c0 += wi * (ka * rgb_s[i * 3 + 0] + q.b * rgb_d[i * 3 + 0]);
+        c1 += wi * (ka * rgb_s[i * 3 + 1] + q.b * rgb_d[i * 3 + 1]);
+        c2 += wi * (ka * rgb_s[i * 3 + 2] + q.b * rgb_d[i * 3 + 2]);
         cs += wi * sh * sh;
     }
     c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2); cs = wave_sum(cs);
@@ -282,24 +325,23 @@ __global__ __launch_bounds__(256) void blend_accumulate_bwd_kernel(const float *
     const float gs = g_shadow ? g_shadow[r] : 0.0f;
     for (int32_t s = lane; s < S; s += kWave) {
         const int64_t i = r * S + s;
-        const float wi = w[i], inv = 1.0f / (sig[i] + 1e-6f);
-        const float ss = sig_s[i], sd = sig_d[i];
-        const float a = ss * inv, b = sd * inv;
+        const float wi = w[i], ss = sig_s[i], sd = sig_d[i];
+        const BlendRatios q = blend_ratios(sig[i], ss, sd);
         const float sh = shadow ? shadow[i] : 0.0f;
         const float s0 = rgb_s[i * 3 + 0], s1 = rgb_s[i * 3 + 1], s2 = rgb_s[i * 3 + 2];
         const float e0 = rgb_d[i * 3 + 0], e1 = rgb_d[i * 3 + 1], e2 = rgb_d[i * 3 + 2];
-        const float ka = a * (1.0f - sh);
+        const float ka = q.a * (1.0f - sh);
         const float gS = g0 * s0 + g1 * s1 + g2 * s2;  // <g, rgb_s>
         const float gD = g0 * e0 + g1 * e1 + g2 * e2;  // <g, rgb_d>
-        if (d_w) d_w[i] = ka * gS + b * gD + gs * sh * sh;
-        const float wka = wi * ka, wb = wi * b;
+        if (d_w) d_w[i] = ka * gS + q.b * gD + gs * sh * sh;
+        const float wka = wi * ka, wb = wi * q.b;
         if (d_rgb_s) { d_rgb_s[i * 3 + 0] = g0 * wka; d_rgb_s[i * 3 + 1] = g1 * wka; d_rgb_s[i * 3 + 2] = g2 * wka; }
         if (d_rgb_d) { d_rgb_d[i * 3 + 0] = g0 * wb; d_rgb_d[i * 3 + 1] = g1 * wb; d_rgb_d[i * 3 + 2] = g2 * wb; }
-        if (d_shadow) d_shadow[i] = wi * (2.0f * gs * sh - a * gS);
-        const float da = wi * (1.0f - sh) * gS, db = wi * gD;
-        if (d_sig_s) d_sig_s[i] = da * inv;
-        if (d_sig_d) d_sig_d[i] = db * inv;
-        if (d_sig) d_sig[i] = -(da * ss + db * sd) * inv * inv;
+        if (d_shadow) d_shadow[i] = wi * (2.0f * gs * sh - q.a * gS);
+        const float da = wi * (1.0f - sh) * gS, db = wi * gD;   // dL/da, dL/db (twin: the tail of blend_accumulate_wide_bwd_kernel)
+        if (d_sig_s) d_sig_s[i] = da * q.inv;
+        if (d_sig_d) d_sig_d[i] = db * q.inv;
+        if (d_sig) d_sig[i] = -(da * ss + db * sd) * q.inv * q.inv;
     }
 }
 
@@ -323,18 +365,17 @@ __global__ __launch_bounds__(256) void blend_accumulate_wide_fwd_kernel(const fl
         int32_t s = wave;
         for (; s + 4 < S; s += 8) {
             const int64_t i = r * S + s, i2 = i + 4;
-            const float inv0 = 1.0f / (sig[i] + 1e-6f), inv1 = 1.0f / (sig[i2] + 1e-6f);
-            const float wa0 = sig_s[i] * inv0, wb0 = sig_d[i] * inv0, wa1 = sig_s[i2] * inv1, wb1 = sig_d[i2] * inv1;
+            const BlendRatios q0 = blend_ratios(sig[i], sig_s[i], sig_d[i]), q1 = blend_ratios(sig[i2], sig_s[i2], sig_d[i2]);
             const float fs0 = on ? f_s[i * C + c] : 0.0f, fd0 = on ? f_d[i * C + c] : 0.0f;
             const float fs1 = on ? f_s[i2 * C + c] : 0.0f, fd1 = on ? f_d[i2 * C + c] : 0.0f;
-            a0 += w[i] * (wa0 * fs0 + wb0 * fd0);
-            a1 += w[i2] * (wa1 * fs1 + wb1 * fd1);
+            a0 += w[i] * (q0.a * fs0 + q0.b * fd0);
+            a1 += w[i2] * (q1.a * fs1 + q1.b * fd1);
         }
         if (s < S) {
             const int64_t i = r * S + s;
-            const float inv = 1.0f / (sig[i] + 1e-6f);
+            const BlendRatios q0 = blend_ratios(sig[i], sig_s[i], sig_d[i]);
             const float fs0 = on ? f_s[i * C + c] : 0.0f, fd0 = on ? f_d[i * C + c] : 0.0f;
-            a0 += w[i] * (sig_s[i] * inv * fs0 + sig_d[i] * inv * fd0);
+            a0 += w[i] * (q0.a * fs0 + q0.b * fd0);
         }
         part[wave][lane] = a0 + a1;
         __syncthreads();
@@ -361,7 +402,7 @@ __global__ __launch_bounds__(256) void blend_accumulate_wide_bwd_kernel(const fl
         for (int u = 0; u < 4; ++u) {
             const int64_t i = q * 4 + u < n ? q * 4 + u : n - 1;
             rr[u] = i / S;
-            const float inv = 1.0f / (sig[i] + 1e-6f);
+            const float inv = 1.0f / (sig[i] + 1e-6f);  // (w * sigma_s) * inv: the feature gradients' own order, not blend_ratios'
             wa[u] = w[i] * sig_s[i] * inv;
             wb[u] = w[i] * sig_d[i] * inv;
         }
@@ -392,6 +433,9 @@ __global__ __launch_bounds__(256) void blend_accumulate_wide_bwd_kernel(const fl
         if (lane < 4 && i < n) {
             const float mS = u == 0 ? gS[0] : u == 1 ? gS[1] : u == 2 ? gS[2] : gS[3];
             const float mD = u == 0 ? gD[0] : u == 1 ? gD[1] : u == 2 ? gD[2] : gD[3];
+            // twin of blend_ratios and of the d_sig tail of blend_accumulate_bwd_kernel, written out: through shared helpers this
+            // kernel read 3 to 5 % above its parent in two sessions, like this it compiles to the parent's instructions
+            // (profiles/composite_dedup_ab.json); change both copies alike
             const float wi = w[i], ss = sig_s[i], sd = sig_d[i], inv = 1.0f / (sig[i] + 1e-6f);
             const float a_ = ss * inv, b_ = sd * inv;
             if (d_w) d_w[i] = a_ * mS + b_ * mD;
@@ -420,63 +464,31 @@ __global__ __launch_bounds__(256) void composite_rgb_fwd_kernel(const float *__r
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kRaysPerBlockC + wave;
     if (r >= R) return;
-    float carry = 0.0f, wsum = 0.0f, wmid = 0.0f, wcarry = 0.0f, median = 0.0f, last_mid = 0.0f;
+    float carry = 0.0f;
     float acc[3] = {0.0f, 0.0f, 0.0f};
-    bool found = false;
+    RayStats stats;
     for (int32_t base = 0; base < S; base += kWave) {
-        const int32_t s = base + lane;
-        const bool ok = s < S;
-        const int64_t i = r * S + s;
-        const float a = ok ? ts[i] : 0.0f, b = ok ? te[i] : 0.0f, sg = ok ? sigma[i] : 0.0f;
+        ScanChunk k = load_chunk(ts, te, sigma, r, S, base, lane);
         float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-        if (ok && rgb) { c0 = rgb[i * 3 + 0]; c1 = rgb[i * 3 + 1]; c2 = rgb[i * 3 + 2]; }
-        const float sdt = sg * (b - a);
-        const float incl = wave_inclusive_sum(sdt, lane);
-        const float excl = carry + (incl - sdt);
-        const float T = expf(-excl);
-        const float al = 1.0f - expf(-sdt);
-        const float w = ok ? T * al : 0.0f;
-        const float mid = (a + b) / 2.0f;
-        if (ok) {
-            weights[i] = w;
-            if (trans) trans[i] = T;
-            if (t_mid) t_mid[i] = mid;
-            if (t_dist) t_dist[i] = b - a;
-            acc[0] += w * c0; acc[1] += w * c1; acc[2] += w * c2;
+        if (k.ok && rgb) { c0 = rgb[k.i * 3 + 0]; c1 = rgb[k.i * 3 + 1]; c2 = rgb[k.i * 3 + 2]; }
+        scan_chunk(k, lane, carry, true);
+        const float w = k.ok ? k.T * (1.0f - k.e) : 0.0f;
+        if (k.ok) {
+            weights[k.i] = w;
+            if (trans) trans[k.i] = k.T;
+            if (t_mid) t_mid[k.i] = k.mid;
+            if (t_dist) t_dist[k.i] = k.dt;
+            acc[0] += w * c0; acc[1] += w * c1; acc[2] += w * c2;   // accumulate_fwd_small<3>: lanes walk samples
         }
-        carry += __shfl(incl, kWave - 1, kWave);
-        const float cw = wcarry + wave_inclusive_sum(w, lane);
-        const unsigned long long hit = __ballot(ok && cw >= 0.5f);
-        if (!found && hit) {
-            const int first = __ffsll((long long)hit) - 1;
-            median = __shfl(mid, first, kWave);
-            found = true;
-        }
-        const int last_lane = (S - 1 - base) < (kWave - 1) ? (S - 1 - base) : (kWave - 1);
-        last_mid = __shfl(mid, last_lane, kWave);
-        wcarry = __shfl(cw, kWave - 1, kWave);
-        wsum += w;
-        wmid += w * mid;
+        carry += __shfl(k.incl, kWave - 1, kWave);
+        stats.step(w, k.mid, k.ok, base, S, lane);
     }
-    wsum = wave_sum(wsum);
-    wmid = wave_sum(wmid);
+    const float4 st = stats.finish();
 #pragma unroll
     for (int c = 0; c < 3; ++c) acc[c] = wave_sum(acc[c]);
     if (lane == 0) {
-        const float med = found ? median : last_mid;
-        *reinterpret_cast<float4 *>(ray_stats + r * 4) = make_float4(wsum, wmid, med, 0.0f);
-        const float o = fminf(fmaxf(wsum, 1e-6f), 1.0f);  // torch.clamp(1e-6, 1.0)
-        opacity[r] = o;
-        depth[r] = wmid / o;
-        if (median_out) median_out[r] = med;
-        if (rgb_out) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = acc[c];
-                if (rgb_sky) v = v + rgb_sky[r * 3 + c] * (1.0f - o);
-                rgb_out[r * 3 + c] = v;
-            }
-        }
+        *reinterpret_cast<float4 *>(ray_stats + r * 4) = st;
+        epilogue_fwd(st, acc, 0, rgb_sky, r, opacity, depth, median_out, rgb_out);
     }
 }
 
@@ -494,70 +506,32 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const float *__r
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kRaysPerBlockC + wave;
     const bool active = r < R;
-    const int32_t n_chunks = (S + kWave - 1) / kWave;
-    if (active) {
-        float carry = 0.0f;
-        for (int32_t c = 0; c < n_chunks; ++c) {
-            const int32_t s = c * kWave + lane;
-            const int64_t i = r * S + s;
-            const float sdt = s < S ? sigma[i] * (te[i] - ts[i]) : 0.0f;
-            if (lane == 0) chunk_base[wave][c] = carry;
-            carry += wave_sum(sdt);
-        }
-    }
+    if (active) fill_chunk_base(ts, te, sigma, r, S, lane, chunk_base[wave]);
     __syncthreads();
     if (!active) return;
-    // per-ray part (ray_epilogue_bwd): gradient of (sum w, sum w mid) and of the accumulated colour
-    const float4 st = *reinterpret_cast<const float4 *>(ray_stats + r * 4);
-    const float o = fminf(fmaxf(st.x, 1e-6f), 1.0f);
-    float go = d_opacity ? d_opacity[r] : 0.0f;
-    const float gd = d_depth ? d_depth[r] : 0.0f;
-    go -= gd * st.y / (o * o);
-    float g[3] = {0.0f, 0.0f, 0.0f};
-    if (d_rgb_out) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            g[c] = d_rgb_out[r * 3 + c];
-            if (rgb_sky) {
-                go -= g[c] * rgb_sky[r * 3 + c];
-                if (d_rgb_sky && lane == 0) d_rgb_sky[r * 3 + c] = g[c] * (1.0f - o);
-            }
-        }
-    }
-    const float g0 = (st.x >= 1e-6f && st.x <= 1.0f) ? go : 0.0f;  // clamp passes the gradient where min <= x <= max (torch semantics)
-    const float g1 = gd / o;
+    // per-ray part (ray_epilogue_bwd, by every lane): gradient of (sum w, sum w mid) and of the accumulated colour
+    const EpilogueGrad eg = epilogue_bwd(*reinterpret_cast<const float4 *>(ray_stats + r * 4), rgb_sky, d_opacity, d_depth, d_rgb_out, r,
+                                         lane == 0, d_rgb_sky);
     float suffix = 0.0f;
-    for (int32_t c = n_chunks - 1; c >= 0; --c) {
-        const int32_t s = c * kWave + lane;
-        const bool ok = s < S;
-        const int64_t i = r * S + s;
-        const float a = ok ? ts[i] : 0.0f, b = ok ? te[i] : 0.0f, sg = ok ? sigma[i] : 0.0f;
-        const float dt = b - a;
-        const float sdt = sg * dt;
-        const float incl = wave_inclusive_sum(sdt, lane);
-        const float excl = chunk_base[wave][c] + (incl - sdt);
-        const float T = expf(-excl);
-        const float e = expf(-sdt);
-        const float w = T * (1.0f - e);
-        float gw = (ok && d_weights) ? d_weights[i] : 0.0f;
-        if (ok && rgb && d_rgb_out) {   // accumulate_bwd: d_w += sum_c g_c rgb_c,  d_rgb = w g
+    for (int32_t c = (S + kWave - 1) / kWave - 1; c >= 0; --c) {
+        ScanChunk k = load_chunk(ts, te, sigma, r, S, c * kWave, lane);
+        scan_chunk(k, lane, chunk_base[wave][c], false);
+        float gw = (k.ok && d_weights) ? d_weights[k.i] : 0.0f;
+        if (k.ok && rgb && d_rgb_out) {   // accumulate_bwd: d_w += sum_c g_c rgb_c,  d_rgb = w g
             float acc = 0.0f;
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) acc += g[ch] * rgb[i * 3 + ch];
+            for (int ch = 0; ch < 3; ++ch) acc += eg.g[ch] * rgb[k.i * 3 + ch];
             gw += acc;
             if (d_rgb) {
-                const float ws = weights[i];
+                const float ws = weights[k.i];
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) d_rgb[i * 3 + ch] = ws * g[ch];
+                for (int ch = 0; ch < 3; ++ch) d_rgb[k.i * 3 + ch] = ws * eg.g[ch];
             }
         }
-        gw += g0 + g1 * ((a + b) / 2.0f);
-        const float gT = (ok && d_trans) ? d_trans[i] : 0.0f;
-        const float term = ok ? gw * w + gT * T : 0.0f;
-        const float sfx_incl = wave_inclusive_suffix_sum(term, lane);
-        const float later = suffix + (sfx_incl - term);
-        if (ok) d_sigma[i] = dt * (gw * T * e - later);
-        suffix += __shfl(sfx_incl, 0, kWave);
+        gw += eg.g0 + eg.g1 * k.mid;
+        const float gT = (k.ok && d_trans) ? d_trans[k.i] : 0.0f;
+        const float da = reverse_chunk(k, gw, gT, lane, suffix);
+        if (k.ok) d_sigma[k.i] = k.dt * da;
     }
 }
 
@@ -565,15 +539,22 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const float *__r
 
 using namespace emer;
 
+// What every entry point ends in: `blocks` workgroups of 256 threads on `stream`, then the launch check under the entry's name.
+template <class K, class... A>
+static int launch256(const char *what, K kern, int64_t blocks, void *stream, A... args) {
+    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, as_stream(stream), args...);
+    return check_launch(what);
+}
+static int64_t ray_blocks(int64_t R) { return ceil_div(R, kRaysPerBlockC); }  // one wave per ray
+
 extern "C" int emer_composite_rgb_fwd(const float *ts, const float *te, const float *sigma, const float *rgb, const float *rgb_sky, int64_t R,
                                       int32_t S, float *weights, float *trans, float *t_mid, float *t_dist, float *ray_stats, float *opacity,
                                       float *depth, float *median_depth, float *rgb_out, void *stream) {
     EMER_REQUIRE(R >= 0 && S >= 1, "composite_rgb_fwd: bad sizes R=%lld S=%d", (long long)R, S);
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(ts && te && sigma && weights && ray_stats && opacity && depth && (!rgb_out || rgb), "composite_rgb_fwd: null pointer");
-    hipLaunchKernelGGL(composite_rgb_fwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream), ts, te, sigma,
-                       rgb_out ? rgb : nullptr, rgb_sky, R, S, weights, trans, t_mid, t_dist, ray_stats, opacity, depth, median_depth, rgb_out);
-    return check_launch("composite_rgb_fwd");
+    return launch256("composite_rgb_fwd", composite_rgb_fwd_kernel, ray_blocks(R), stream, ts, te, sigma, rgb_out ? rgb : nullptr, rgb_sky, R, S,
+                     weights, trans, t_mid, t_dist, ray_stats, opacity, depth, median_depth, rgb_out);
 }
 
 extern "C" int emer_composite_rgb_bwd(const float *ts, const float *te, const float *sigma, const float *rgb, const float *rgb_sky,
@@ -583,9 +564,8 @@ extern "C" int emer_composite_rgb_bwd(const float *ts, const float *te, const fl
     EMER_REQUIRE(R >= 0 && S >= 1 && S <= 4096, "composite_rgb_bwd: bad sizes R=%lld S=%d (S <= 4096)", (long long)R, S);
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(ts && te && sigma && ray_stats && d_sigma && (!d_rgb || (rgb && weights && d_rgb_out)), "composite_rgb_bwd: null pointer");
-    hipLaunchKernelGGL(composite_rgb_bwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream), ts, te, sigma, rgb,
-                       rgb_sky, weights, ray_stats, d_rgb_out, d_opacity, d_depth, d_weights, d_trans, R, S, d_sigma, d_rgb, d_rgb_sky);
-    return check_launch("composite_rgb_bwd");
+    return launch256("composite_rgb_bwd", composite_rgb_bwd_kernel, ray_blocks(R), stream, ts, te, sigma, rgb, rgb_sky, weights, ray_stats,
+                     d_rgb_out, d_opacity, d_depth, d_weights, d_trans, R, S, d_sigma, d_rgb, d_rgb_sky);
 }
 
 extern "C" int emer_blend_accumulate_wide_fwd(const float *weights, const float *density, const float *static_density, const float *dynamic_density,
@@ -594,9 +574,8 @@ extern "C" int emer_blend_accumulate_wide_fwd(const float *weights, const float 
     EMER_REQUIRE(R >= 0 && S >= 1 && C >= 1, "blend_accumulate_wide_fwd: bad sizes");
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(weights && density && static_density && dynamic_density && static_feat && dynamic_feat && acc, "blend_accumulate_wide_fwd: null pointer");
-    hipLaunchKernelGGL(blend_accumulate_wide_fwd_kernel, dim3((uint32_t)R), dim3(256), 0, as_stream(stream), weights, density,
-                       static_density, dynamic_density, static_feat, dynamic_feat, R, S, C, acc);
-    return check_launch("blend_accumulate_wide_fwd");
+    return launch256("blend_accumulate_wide_fwd", blend_accumulate_wide_fwd_kernel, R, stream, weights, density, static_density, dynamic_density,
+                     static_feat, dynamic_feat, R, S, C, acc);   // one workgroup per ray
 }
 
 extern "C" int emer_blend_accumulate_wide_bwd(const float *weights, const float *density, const float *static_density, const float *dynamic_density,
@@ -607,10 +586,9 @@ extern "C" int emer_blend_accumulate_wide_bwd(const float *weights, const float 
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(weights && density && static_density && dynamic_density && static_feat && dynamic_feat && d_acc, "blend_accumulate_wide_bwd: null pointer");
     const int64_t wg = ceil_div(R * (int64_t)S, 4 * 8);   // ~two quads of samples per wave
-    hipLaunchKernelGGL(blend_accumulate_wide_bwd_kernel, dim3((uint32_t)(wg > 16384 ? 16384 : wg)), dim3(256), 0, as_stream(stream), weights, density,
-                       static_density, dynamic_density, static_feat, dynamic_feat, d_acc, R, S, C, d_weights, d_density, d_static_density,
-                       d_dynamic_density, d_static_feat, d_dynamic_feat);
-    return check_launch("blend_accumulate_wide_bwd");
+    return launch256("blend_accumulate_wide_bwd", blend_accumulate_wide_bwd_kernel, wg > 16384 ? 16384 : wg, stream, weights, density, static_density,
+                     dynamic_density, static_feat, dynamic_feat, d_acc, R, S, C, d_weights, d_density, d_static_density, d_dynamic_density,
+                     d_static_feat, d_dynamic_feat);
 }
 
 extern "C" int emer_render_weights_fwd(const float *ts, const float *te, const float *sigma, int64_t R, int32_t S,
@@ -619,9 +597,8 @@ extern "C" int emer_render_weights_fwd(const float *ts, const float *te, const f
     EMER_REQUIRE(R >= 0 && S >= 1, "render_weights_fwd: bad sizes R=%lld S=%d", (long long)R, S);
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(ts && te && sigma, "render_weights_fwd: null input");
-    hipLaunchKernelGGL(render_weights_fwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream),
-                       ts, te, sigma, R, S, weights, trans, alphas, cdfs, ray_stats, t_mid, t_dist);
-    return check_launch("render_weights_fwd");
+    return launch256("render_weights_fwd", render_weights_fwd_kernel, ray_blocks(R), stream, ts, te, sigma, R, S, weights, trans, alphas, cdfs,
+                     ray_stats, t_mid, t_dist);
 }
 
 extern "C" int emer_render_weights_bwd(const float *ts, const float *te, const float *sigma, const float *d_weights,
@@ -630,9 +607,8 @@ extern "C" int emer_render_weights_bwd(const float *ts, const float *te, const f
     EMER_REQUIRE(R >= 0 && S >= 1 && S <= 4096, "render_weights_bwd: bad sizes R=%lld S=%d (S <= 4096)", (long long)R, S);
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(ts && te && sigma && d_sigma, "render_weights_bwd: null pointer");
-    hipLaunchKernelGGL(render_weights_bwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream),
-                       ts, te, sigma, d_weights, d_trans, d_alphas, d_ray_stats, R, S, d_sigma);
-    return check_launch("render_weights_bwd");
+    return launch256("render_weights_bwd", render_weights_bwd_kernel, ray_blocks(R), stream, ts, te, sigma, d_weights, d_trans, d_alphas,
+                     d_ray_stats, R, S, d_sigma);
 }
 
 extern "C" int emer_accumulate_fwd(const float *w, const float *v, int64_t R, int32_t S, int32_t C, float *out,
@@ -641,15 +617,12 @@ extern "C" int emer_accumulate_fwd(const float *w, const float *v, int64_t R, in
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(w && out, "accumulate_fwd: null pointer");
     EMER_REQUIRE(v || C == 1, "accumulate_fwd: values == NULL requires n_channels == 1");
-    const dim3 grid((uint32_t)ceil_div(R, kRaysPerBlockC)), block(256);
-    hipStream_t st = as_stream(stream);
     switch (C) {
-#define EMER_ACC(c) case c: hipLaunchKernelGGL(accumulate_fwd_small_kernel<c>, grid, block, 0, st, w, v, R, S, out); break;
+#define EMER_ACC(c) case c: return launch256("accumulate_fwd", accumulate_fwd_small_kernel<c>, ray_blocks(R), stream, w, v, R, S, out);
         EMER_ACC(1) EMER_ACC(2) EMER_ACC(3) EMER_ACC(4) EMER_ACC(5) EMER_ACC(6) EMER_ACC(7) EMER_ACC(8)
 #undef EMER_ACC
-        default: hipLaunchKernelGGL(accumulate_fwd_wide_kernel, grid, block, 0, st, w, v, R, S, C, out);
     }
-    return check_launch("accumulate_fwd");
+    return launch256("accumulate_fwd", accumulate_fwd_wide_kernel, ray_blocks(R), stream, w, v, R, S, C, out);
 }
 
 extern "C" int emer_accumulate_bwd(const float *w, const float *v, const float *d_out, int64_t R, int32_t S, int32_t C,
@@ -658,20 +631,12 @@ extern "C" int emer_accumulate_bwd(const float *w, const float *v, const float *
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(w && d_out, "accumulate_bwd: null pointer");
     EMER_REQUIRE(v || (C == 1 && !d_v), "accumulate_bwd: values == NULL requires n_channels == 1 and d_values == NULL");
-    hipStream_t st = as_stream(stream);
-    const dim3 block(256);
-    if (C <= 8) {
-        const dim3 grid((uint32_t)ceil_div(R * S, 256));
-        switch (C) {
-#define EMER_ACC(c) case c: hipLaunchKernelGGL(accumulate_bwd_small_kernel<c>, grid, block, 0, st, w, v, d_out, R, S, d_w, d_v); break;
-            EMER_ACC(1) EMER_ACC(2) EMER_ACC(3) EMER_ACC(4) EMER_ACC(5) EMER_ACC(6) EMER_ACC(7) EMER_ACC(8)
+    switch (C) {   // small: one thread per (ray, sample)
+#define EMER_ACC(c) case c: return launch256("accumulate_bwd", accumulate_bwd_small_kernel<c>, ceil_div(R * S, 256), stream, w, v, d_out, R, S, d_w, d_v);
+        EMER_ACC(1) EMER_ACC(2) EMER_ACC(3) EMER_ACC(4) EMER_ACC(5) EMER_ACC(6) EMER_ACC(7) EMER_ACC(8)
 #undef EMER_ACC
-        }
-    } else {
-        hipLaunchKernelGGL(accumulate_bwd_wide_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), block, 0, st, w, v, d_out, R,
-                           S, C, d_w, d_v);
     }
-    return check_launch("accumulate_bwd");
+    return launch256("accumulate_bwd", accumulate_bwd_wide_kernel, ray_blocks(R), stream, w, v, d_out, R, S, C, d_w, d_v);
 }
 
 extern "C" int emer_blend_accumulate_fwd(const float *weights, const float *density, const float *static_density,
@@ -682,9 +647,8 @@ extern "C" int emer_blend_accumulate_fwd(const float *weights, const float *dens
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(weights && density && static_density && dynamic_density && static_rgb && dynamic_rgb && acc_rgb, "blend_accumulate_fwd: null pointer");
     EMER_REQUIRE(!acc_shadow_sq || shadow_ratio, "blend_accumulate_fwd: acc_shadow_sq needs shadow_ratio");
-    hipLaunchKernelGGL(blend_accumulate_fwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream), weights,
-                       density, static_density, dynamic_density, static_rgb, dynamic_rgb, shadow_ratio, R, S, acc_rgb, acc_shadow_sq);
-    return check_launch("blend_accumulate_fwd");
+    return launch256("blend_accumulate_fwd", blend_accumulate_fwd_kernel, ray_blocks(R), stream, weights, density, static_density, dynamic_density,
+                     static_rgb, dynamic_rgb, shadow_ratio, R, S, acc_rgb, acc_shadow_sq);
 }
 
 extern "C" int emer_blend_accumulate_bwd(const float *weights, const float *density, const float *static_density,
@@ -697,8 +661,7 @@ extern "C" int emer_blend_accumulate_bwd(const float *weights, const float *dens
     if (R == 0) return EMER_OK;
     EMER_REQUIRE(weights && density && static_density && dynamic_density && static_rgb && dynamic_rgb, "blend_accumulate_bwd: null pointer");
     EMER_REQUIRE(!d_shadow_ratio || shadow_ratio, "blend_accumulate_bwd: d_shadow_ratio needs shadow_ratio");
-    hipLaunchKernelGGL(blend_accumulate_bwd_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlockC)), dim3(256), 0, as_stream(stream), weights,
-                       density, static_density, dynamic_density, static_rgb, dynamic_rgb, shadow_ratio, d_acc_rgb, d_acc_shadow_sq, R, S,
-                       d_weights, d_density, d_static_density, d_dynamic_density, d_static_rgb, d_dynamic_rgb, d_shadow_ratio);
-    return check_launch("blend_accumulate_bwd");
+    return launch256("blend_accumulate_bwd", blend_accumulate_bwd_kernel, ray_blocks(R), stream, weights, density, static_density, dynamic_density,
+                     static_rgb, dynamic_rgb, shadow_ratio, d_acc_rgb, d_acc_shadow_sq, R, S, d_weights, d_density, d_static_density,
+                     d_dynamic_density, d_static_rgb, d_dynamic_rgb, d_shadow_ratio);
 }

@@ -6,31 +6,23 @@
 // "opacity_based" = binary cross entropy between opacity and 1 - sky_mask, coefficient 0.001 in
 // configs/default_config.yaml) together with their autograd graphs: about 25 elementwise launches per step on
 // [R, 1..3] tensors become two forward and two backward launches.  SURVEY.md section 8f row N4 (per-ray part).
+// The epilogue's arithmetic itself lives in ray_epilogue.h, one copy: the two kernels below run it per thread, and
+// composite_rgb_fwd/bwd (composite.hip) run the same functions per wave, so the fused and the unfused path cannot drift apart.
 #include "common.h"
+#include "ray_epilogue.h"
 
 namespace emer {
 
 // ---------------------------------------------------------------------------------------------- ray epilogue
-// stats [R,4] = (sum w, sum w*mid, median depth, -) from emer_render_weights_fwd.
+// stats [R,4] = (sum w, sum w*mid, median depth, -) from emer_render_weights_fwd; read through epilogue_fwd / epilogue_bwd of
+// ray_epilogue.h, which composite_rgb shares.
 __global__ __launch_bounds__(256) void ray_epilogue_fwd_kernel(const float *__restrict__ stats, const float *__restrict__ acc_rgb,
                                                                const float *__restrict__ rgb_sky, int64_t R,
                                                                float *__restrict__ opacity, float *__restrict__ depth,
                                                                float *__restrict__ median, float *__restrict__ rgb) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= R) return;
-    const float4 st = *reinterpret_cast<const float4 *>(stats + r * 4);
-    const float o = fminf(fmaxf(st.x, 1e-6f), 1.0f);  // torch.clamp(1e-6, 1.0)
-    opacity[r] = o;
-    depth[r] = st.y / o;
-    if (median) median[r] = st.z;
-    if (rgb) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v = acc_rgb[r * 3 + c];
-            if (rgb_sky) v = v + rgb_sky[r * 3 + c] * (1.0f - o);
-            rgb[r * 3 + c] = v;
-        }
-    }
+    epilogue_fwd(*reinterpret_cast<const float4 *>(stats + r * 4), acc_rgb, r * 3, rgb_sky, r, opacity, depth, median, rgb);
 }
 
 // d_stats [R,4] = gradient of ray_stats (columns 2, 3 zero); d_rgb_sky [R,3].  The gradient of acc_rgb is d_rgb itself.
@@ -40,21 +32,8 @@ __global__ __launch_bounds__(256) void ray_epilogue_bwd_kernel(const float *__re
                                                                float *__restrict__ d_rgb_sky) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= R) return;
-    const float4 st = *reinterpret_cast<const float4 *>(stats + r * 4);
-    const float o = fminf(fmaxf(st.x, 1e-6f), 1.0f);
-    float go = d_opacity ? d_opacity[r] : 0.0f;
-    const float gd = d_depth ? d_depth[r] : 0.0f;
-    go -= gd * st.y / (o * o);
-    if (d_rgb && rgb_sky) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float g = d_rgb[r * 3 + c];
-            go -= g * rgb_sky[r * 3 + c];
-            if (d_rgb_sky) d_rgb_sky[r * 3 + c] = g * (1.0f - o);
-        }
-    }
-    // clamp passes the gradient where min <= x <= max (torch semantics, bounds included)
-    *reinterpret_cast<float4 *>(d_stats + r * 4) = make_float4((st.x >= 1e-6f && st.x <= 1.0f) ? go : 0.0f, gd / o, 0.0f, 0.0f);
+    const EpilogueGrad e = epilogue_bwd(*reinterpret_cast<const float4 *>(stats + r * 4), rgb_sky, d_opacity, d_depth, d_rgb, r, true, d_rgb_sky);
+    *reinterpret_cast<float4 *>(d_stats + r * 4) = make_float4(e.g0, e.g1, 0.0f, 0.0f);
 }
 
 // ------------------------------------------------------------------------------------------------ pixel losses

@@ -43,6 +43,16 @@ def _f32c(t: Tensor) -> Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+def _opt(t: Optional[Tensor]) -> Optional[Tensor]:
+    """_f32c of an optional tensor (an absent input or gradient stays None: a null pointer for the kernel)."""
+    return None if t is None else _f32c(t)
+
+
+def _empty(ref: Tensor, *shape) -> Tensor:
+    """Uninitialised fp32 output on ``ref``'s device."""
+    return torch.empty(shape, device=ref.device, dtype=torch.float32)
+
+
 def _dtype_tag(t: Tensor) -> int:
     if t.dtype == torch.float32:
         return F32
@@ -609,8 +619,7 @@ class _RenderWeightsFn(torch.autograd.Function):
         R, S = sg.shape
         with torch.cuda.device(sg.device):
             w, T, a = (torch.empty_like(sg) for _ in range(3))
-            cdfs = torch.empty((R, S + 1), device=sg.device, dtype=torch.float32)
-            stats = torch.empty((R, 4), device=sg.device, dtype=torch.float32)
+            cdfs, stats = _empty(sg, R, S + 1), _empty(sg, R, 4)
             tm, td = (torch.empty_like(sg), torch.empty_like(sg)) if want_t else (None, None)
             _lib.call("emer_render_weights_fwd", _ptr(ts), _ptr(te), _ptr(sg), R, S, _ptr(w), _ptr(T), _ptr(a), _ptr(cdfs),
                       _ptr(stats), _ptr(tm), _ptr(td), _stream(sg))
@@ -624,15 +633,10 @@ class _RenderWeightsFn(torch.autograd.Function):
     def backward(ctx, dw, dT, da, dcdfs, dstats, *_unused):
         ts, te, sg = ctx.saved_tensors
         R, S = sg.shape
-        gT = None
-        if dT is not None:
-            gT = _f32c(dT)
+        gw, gT, ga, gs = _opt(dw), _opt(dT), _opt(da), _opt(dstats)  # gs [R,4]: the kernel reads columns 0, 1
         if dcdfs is not None:  # cdfs = 1 - [T, 0]
             g = -_f32c(dcdfs)[:, :S]
             gT = g.contiguous() if gT is None else gT + g
-        gw = None if dw is None else _f32c(dw)
-        ga = None if da is None else _f32c(da)
-        gs = None if dstats is None else _f32c(dstats)  # [R,4]; the kernel reads columns 0, 1
         if gw is None and gT is None and gs is None and ga is None:
             return None, None, None, None
         with torch.cuda.device(sg.device):
@@ -663,9 +667,9 @@ class _CompositeRgbFn(torch.autograd.Function):
         sk = None if (rgb_sky is None or rgb is None) else _f32c(rgb_sky).reshape(R, 3)
         with torch.cuda.device(sg.device):
             w, T, tm, td = (torch.empty_like(sg) for _ in range(4))
-            stats = torch.empty((R, 4), device=sg.device, dtype=torch.float32)
-            opa, dep, med = (torch.empty((R, 1), device=sg.device, dtype=torch.float32) for _ in range(3))
-            out = torch.empty((R, 3), device=sg.device, dtype=torch.float32) if c is not None else None
+            stats = _empty(sg, R, 4)
+            opa, dep, med = (_empty(sg, R, 1) for _ in range(3))
+            out = _empty(sg, R, 3) if c is not None else None
             _lib.call("emer_composite_rgb_fwd", _ptr(ts), _ptr(te), _ptr(sg), _ptr(c), _ptr(sk), R, S, _ptr(w), _ptr(T), _ptr(tm), _ptr(td),
                       _ptr(stats), _ptr(opa), _ptr(dep), _ptr(med), _ptr(out), _stream(sg))
         ctx.save_for_backward(ts, te, sg, c, sk, w, stats)
@@ -678,8 +682,7 @@ class _CompositeRgbFn(torch.autograd.Function):
         R, S = sg.shape
         if all(g is None for g in (dw, dT, dopa, ddep, dout)):
             return None, None, None, None, None
-        f = lambda g: None if g is None else _f32c(g)
-        gw, gT, go, gd, gr = f(dw), f(dT), f(dopa), f(ddep), f(dout)
+        gw, gT, go, gd, gr = _opt(dw), _opt(dT), _opt(dopa), _opt(ddep), _opt(dout)
         need_rgb = c is not None and ctx.needs_input_grad[3] and gr is not None
         need_sky = sk is not None and ctx.needs_input_grad[4] and gr is not None
         with torch.cuda.device(sg.device):
@@ -707,10 +710,10 @@ class _AccumulateFn(torch.autograd.Function):
     def forward(ctx, weights: Tensor, values: Optional[Tensor]):
         w = _f32c(weights)
         R, S = w.shape
-        v = None if values is None else _f32c(values)
+        v = _opt(values)
         C = 1 if v is None else v.shape[-1]
         with torch.cuda.device(w.device):
-            out = torch.empty((R, C), device=w.device, dtype=torch.float32)
+            out = _empty(w, R, C)
             _lib.call("emer_accumulate_fwd", _ptr(w), _ptr(v), R, S, C, _ptr(out), _stream(w))
         ctx.save_for_backward(w, v)
         return out
@@ -745,11 +748,10 @@ class _RayEpilogueFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         st = _f32c(stats)
         R = st.shape[0]
-        ar = None if acc_rgb is None else _f32c(acc_rgb)
-        sk = None if rgb_sky is None else _f32c(rgb_sky)
+        ar, sk = _opt(acc_rgb), _opt(rgb_sky)
         with torch.cuda.device(st.device):
-            opa, dep, med = (torch.empty((R, 1), device=st.device, dtype=torch.float32) for _ in range(3))
-            rgb = torch.empty((R, 3), device=st.device, dtype=torch.float32) if ar is not None else None
+            opa, dep, med = (_empty(st, R, 1) for _ in range(3))
+            rgb = _empty(st, R, 3) if ar is not None else None
             _lib.call("emer_ray_epilogue_fwd", _ptr(st), _ptr(ar), _ptr(sk), R, _ptr(opa), _ptr(dep), _ptr(med), _ptr(rgb), _stream(st))
         ctx.save_for_backward(st, sk)
         ctx.has_rgb = ar is not None
@@ -762,12 +764,10 @@ class _RayEpilogueFn(torch.autograd.Function):
         R = st.shape[0]
         if do is None and dd is None and drgb is None:
             return None, None, None
-        go = None if do is None else _f32c(do)
-        gd = None if dd is None else _f32c(dd)
-        gr = None if drgb is None else _f32c(drgb)
+        go, gd, gr = _opt(do), _opt(dd), _opt(drgb)
         with torch.cuda.device(st.device):
-            dst = torch.empty((R, 4), device=st.device, dtype=torch.float32)
-            dsk = torch.empty((R, 3), device=st.device, dtype=torch.float32) if (sk is not None and gr is not None) else None
+            dst = _empty(st, R, 4)
+            dsk = _empty(st, R, 3) if (sk is not None and gr is not None) else None
             _lib.call("emer_ray_epilogue_bwd", _ptr(st), _ptr(sk), _ptr(go), _ptr(gd), _ptr(gr), R, _ptr(dst), _ptr(dsk), _stream(st))
         return dst, (gr if ctx.has_rgb else None), dsk
 

@@ -7,6 +7,7 @@ tests/test_composite_bounds_cpu.py shows what the probes catch (the numpy model 
   entry, at S from 1 to 4096 (chunk_base exactly full), partial workgroups, every residue of the wide loops;
 * realistic rays: every entry of every output and gradient inside its first-order bound, the median exact, composite_rgb
   against the fp64 restatement directly; the worst err / bound is printed per output (DESIGN.md 4.4 records them);
+* what the kernels' shared stages rely on: a null optional output or upstream gradient changes no other result;
 * the argument contract of the entry points.
 """
 import numpy as np
@@ -225,6 +226,68 @@ def test_device_expf_error_is_inside_E_EXPF(hip_lib):
           f"{float(err[~normal].max()):.3e} absolute")
     assert worst <= B.E_EXPF - 1.0
     assert float(err[~normal].max()) <= B.TINY
+
+
+# ------------------------------------------------------------------------------- what the shared stages rely on
+@pytest.mark.parametrize("R,S", [(5, 1), (5, 65), (13, 129)])
+def test_optional_pointers_do_not_change_the_other_results(hip_lib, R, S):
+    """The scan kernels share one chunk function, one ray-statistics accumulator and one reverse chunk whatever the caller asks
+    for, so through the C entry points: every output of emer_render_weights_fwd / emer_composite_rgb_fwd is bitwise the same with
+    the other optional outputs requested as with them null, and d_sigma of both backwards is bitwise the same with an upstream
+    pointer null as with it pointing at zeros."""
+    from emernerf_amd import _lib
+    from emernerf_amd.ops import _ptr, _stream
+    p = {k: _d(v) for k, v in P.realistic(R, S).items()}
+    ts, te, sg, st = p["ts"], p["te"], p["sg"], _stream(p["sg"])
+    new = lambda *shape: torch.full(shape, 7.5, device=DEV)  # noqa: E731
+
+    def render_fwd(want):
+        o = {k: (new(R, S + 1) if k == "cdfs" else new(R, 4) if k == "ray_stats" else new(R, S)) if k in want else None
+             for k in ("weights", "trans", "alphas", "cdfs", "ray_stats", "t_mid", "t_dist")}
+        _lib.call("emer_render_weights_fwd", _ptr(ts), _ptr(te), _ptr(sg), R, S, *(_ptr(o[k]) for k in o), st)
+        return o
+
+    full = render_fwd(("weights", "trans", "alphas", "cdfs", "ray_stats", "t_mid", "t_dist"))
+    for k in full:
+        assert torch.equal(render_fwd((k,))[k], full[k]), f"render_weights_fwd: {k} alone differs from {k} among all outputs"
+
+    need = ("weights", "ray_stats", "opacity", "depth")
+    shapes = dict(weights=(R, S), trans=(R, S), t_mid=(R, S), t_dist=(R, S), ray_stats=(R, 4), opacity=(R,), depth=(R,), median_depth=(R,), rgb_out=(R, 3))
+
+    def composite_fwd(want):
+        o = {k: new(*shape) if (k in want or k in need) else None for k, shape in shapes.items()}
+        _lib.call("emer_composite_rgb_fwd", _ptr(ts), _ptr(te), _ptr(sg), _ptr(p["rgb"]), _ptr(p["sky"]), R, S, *(_ptr(o[k]) for k in o), st)
+        return o
+
+    cfull = composite_fwd(tuple(shapes))
+    for k in ("trans", "t_mid", "t_dist", "median_depth", "rgb_out"):
+        got = composite_fwd((k,))
+        for name in need + (k,):
+            assert torch.equal(got[name], cfull[name]), f"composite_rgb_fwd: {name} with only {k} requested differs"
+    got = composite_fwd(())
+    for name in need:
+        assert torch.equal(got[name], cfull[name]), f"composite_rgb_fwd: {name} with no optional output differs"
+
+    ups = dict(d_weights=p["dW"], d_trans=p["dT"], d_alphas=p["dA"], d_ray_stats=p["dS"])
+
+    def render_bwd(g):
+        ds = new(R, S)
+        _lib.call("emer_render_weights_bwd", _ptr(ts), _ptr(te), _ptr(sg), *(_ptr(g[k]) for k in ups), R, S, _ptr(ds), st)
+        return ds
+
+    for k in ups:
+        assert torch.equal(render_bwd({**ups, k: None}), render_bwd({**ups, k: torch.zeros_like(ups[k])})), f"render_weights_bwd: {k} null vs zeros"
+
+    cups = dict(d_rgb_out=p["d_out"], d_opacity=p["d_opa"], d_depth=p["d_dep"], d_weights=p["dW"], d_trans=p["dT"])
+
+    def composite_bwd(g):
+        ds = new(R, S)
+        _lib.call("emer_composite_rgb_bwd", _ptr(ts), _ptr(te), _ptr(sg), _ptr(p["rgb"]), _ptr(p["sky"]), _ptr(cfull["weights"]), _ptr(cfull["ray_stats"]),
+                  *(_ptr(g[k]) for k in cups), R, S, _ptr(ds), None, None, st)
+        return ds
+
+    for k in cups:
+        assert torch.equal(composite_bwd({**cups, k: None}), composite_bwd({**cups, k: torch.zeros_like(cups[k])})), f"composite_rgb_bwd: {k} null vs zeros"
 
 
 # -------------------------------------------------------------------------------------------------- argument contract

@@ -1166,9 +1166,18 @@ def dir_encode(dirs: Tensor, max_deg: int = 4, remap: bool = True) -> Tensor:
 
 def adam_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, lr: float, beta1: float, beta2: float,
               eps: float, weight_decay: float, grad_scale: float, step: int) -> None:
-    """In-place torch.optim.Adam step on one flat fp32 buffer."""
+    """In-place torch.optim.Adam step on one flat fp32 buffer.  The kernel reads and writes ``params.numel()`` floats of all four
+    tensors through raw pointers, so each must be fp32, contiguous, on ``params``' device and of that length."""
     _check_cuda(params, grads, exp_avg, exp_avg_sq)
-    assert params.is_contiguous() and grads.is_contiguous() and params.dtype == torch.float32
+    for name, t in (("params", params), ("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.dtype != torch.float32:
+            raise _lib.EmerError(f"adam_step: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.EmerError(f"adam_step: {name} must be contiguous")
+        if t.device != params.device:
+            raise _lib.EmerError(f"adam_step: {name} is on {t.device}, params on {params.device}")
+        if t.numel() != params.numel():
+            raise _lib.EmerError(f"adam_step: {name} has {t.numel()} elements, params {params.numel()}")
     with torch.cuda.device(params.device):
         _lib.call("emer_adam_step", _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), params.numel(), float(lr),
                   float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale), int(step), _stream(params))

@@ -748,3 +748,114 @@ def c_embed_grad(n_rays: int) -> float:
 # 2.36 -> 4).  tests/test_ray_exact_gpu.py::test_device_sinf_error_is_inside_E_SINF runs sinf_sweep(17) in the suite.
 E_SINF_MEASURED = 1.572  # ulps
 E_SINF = 4.0
+
+
+# ------------------------------------------------------------------------------- update kernels of csrc/elementwise.hip
+# emer_adam_step, emer_contract_bwd and emer_flow_warp_bwd on arbitrary fp32 inputs (tests/_update_probe.py has the fp64
+# restatements whose intermediates these take).  Running-error bounds to first order: every fp32 operation adds u times the
+# size of its own result to the error its operands already carry, and that error travels on through the derivative of the
+# next operation.  The file forbids FMA contraction (every product and sum rounds on its own), and the project's compiler
+# flags (-O3, no fast-math option, no option that relaxes division or square root: emernerf_amd/_build.py) leave the
+# division and sqrtf correctly rounded, so every operation costs exactly one u and NOTHING here is measured.  Hyperparameters
+# enter the restatement as the c_float values the ABI receives and so carry no error of their own; the two bias corrections
+# are formed in double on the host and narrowed to float: one u each.  Where a denominator or a root's argument carries an
+# error the rigorous form is used instead of the derivative (a / (b - e_b), e / (sqrt x + sqrt(x - e))): it equals the
+# first-order term when the error is small and stays an upper bound when a cancellation in g gs + wd p made it large.
+UPDATE_SLACK = 1.5       # second-order terms of the remaining products, and the fp64 restatement's own roundings
+UPDATE_FLOOR = 2.0 ** -149   # a product or quotient that leaves the normal range rounds to this grid instead of to u |x|
+
+
+def _r(x):
+    """The rounding of one fp32 operation whose exact result is x (an exact zero stays exact)."""
+    return U * np.abs(x) + np.where(np.asarray(x) != 0, UPDATE_FLOOR, 0.0)
+
+
+def adam_bounds(st: dict) -> dict:
+    """Absolute bounds on m', v', p' of one emer_adam_step from ``restate_adam``'s intermediates.  In the kernel's order:
+
+    * gi = fl(g gs) [1; exact for gs = 1], + fl(wd p) [1] and the sum [1] when wd != 0;
+    * m' = m + fl(fl(gi - m) fl(1 - b1)): the difference 1, fl(1 - b1) 1 and the product 1 (3 u on the product, the
+      difference's share through the factor 1 - b1), the sum 1;
+    * v' = fl(v b2) + fl(fl(fl(1 - b2) gi) gi): v b2 1; fl(1 - b2) and two products 3, the error of gi twice (2 |gi| e + e^2);
+      the sum 1;
+    * s = sqrtf(v'): e_v / (sqrt v' + sqrt(v' - e_v)) + u s  (= e_v / (2 sqrt v') to first order);
+    * denom = fl(s / bc2_sqrt) + eps: the narrowed bc2_sqrt 1 and the division 1, the sum 1;
+    * r = fl(m' / denom): (e_m + |r| e_denom) / (denom - e_denom) + u |r|;
+    * p' = p - fl(step_size r), step_size = fl(lr / fl(bc1)): the narrowed bc1, the division and the product 3, the
+      difference 1."""
+    a = np.abs
+    c = st["c"]
+    e_gi = np.zeros_like(st["gi"]) if c["gs"] == 1.0 else _r(st["g_gs"])
+    if c["wd"] != 0.0:
+        e_gi = e_gi + _r(st["wd_p"]) + _r(st["gi"])
+    omb1, omb2 = 1.0 - c["b1"], 1.0 - c["b2"]
+    e_m = omb1 * (e_gi + _r(st["d"])) + 2 * _r(st["d"] * omb1) + _r(st["m1"])
+    e_v = _r(st["v_b2"]) + omb2 * (2 * a(st["gi"]) * e_gi + e_gi ** 2) + 3 * _r(st["g2"]) + _r(st["v1"])
+    s = st["s"]
+    e_s = e_v / np.maximum(s + np.sqrt(np.maximum(st["v1"] - e_v, 0.0)), 1e-300) + _r(s)
+    e_s = np.where(e_v == 0.0, _r(s), e_s)
+    e_den = e_s / c["bc2_sqrt"] + 2 * _r(st["s_bc"]) + _r(st["denom"])
+    lo = st["denom"] - e_den
+    assert (lo > 0).all(), "adam_bounds: a denominator's error reaches its size"
+    e_r = (e_m + a(st["r"]) * e_den) / lo + _r(st["r"])
+    e_p = c["step_size"] * e_r + 3 * _r(st["upd"]) + _r(st["p1"])
+    return dict(m=UPDATE_SLACK * e_m, v=UPDATE_SLACK * e_v, p=UPDATE_SLACK * e_p)
+
+
+def contract_bwd_bounds(st: dict) -> np.ndarray:
+    """Absolute bound [n, 3] on emer_contract_bwd's gradient from ``restate_contract_bwd``'s intermediates; st["e_p"] /
+    st["e_g"] are errors the position / the incoming gradient already carry (0 for the kernel's own inputs).  A point the fp32
+    forward puts outside has the bound 0: its gradient is exactly 0.
+
+    * bounded, and unbounded with mag < 1 (out = g / w, resp. fl(fl(g / 4) 2) / w: the power-of-two steps are exact): the
+      width fl(hi - lo) 1 and the division 1 -> 2 u |out| + e_g's share;
+    * unbounded, mag >= 1:  a = fl(p - lo) 1;  b = fl(a / w) 2;  u = fl(2 b - 1) 1 (2 b exact) -> e_u = 2 e_b + u |u|;
+      mag = |u_k|;  inv = fl(1 / mag): e_mag / (mag (mag - e_mag)) + u inv;
+      f = fl(2 inv - fl(inv inv)): 2 e_inv + (2 inv e_inv + u inv^2) + u |f|;
+      df = fl(fl(-2 inv inv) + fl(fl(2 inv inv) inv)): 4 inv e_inv + u |A|, 6 inv^2 e_inv + 2 u |B|, the sum 1;
+      dotug = (t_0 + t_1) + t_2 with t_d = fl(u_d g_d / 4): |g_d / 4| e_u + |u_d| e_g / 4 + u |t_d| each, two sums <= 2 u sum |t_d|;
+      term = fl(sgn df dotug): |dotug| e_df + |df| e_dot + e_df e_dot + u |term|;
+      gu_d = fl(f g_d / 4) [|g_d / 4| e_f + |f| e_g / 4 + u] (+ term on axis k: e_term + u |gu_k|);
+      out_d = fl(2 gu_d / w_d): the width 1, the division 1."""
+    a = np.abs
+    w, out = a(st["w"])[None, :], st["out"]
+    e_g = np.broadcast_to(np.asarray(st.get("e_g", 0.0), np.float64), out.shape)
+    inside = st["inside"][:, None]
+    if not st["unbounded"]:
+        return np.where(inside, UPDATE_SLACK * (e_g / w + 2 * _r(out)), 0.0)
+    ge1 = st["ge1"]
+    e_p = np.broadcast_to(np.asarray(st.get("e_p", 0.0), np.float64), out.shape)
+    e_a = e_p + _r(st["a"])
+    e_b = e_a / w + 2 * _r(st["b"])
+    e_u = 2 * e_b + _r(st["u"])
+    k = st["k"][:, None]
+    e_mag = np.take_along_axis(e_u, k, 1)[:, 0]
+    mag, inv, f, df = st["mag"], st["inv"], st["f"], st["df"]
+    assert (e_mag[ge1] < 0.5 * mag[ge1]).all(), "contract_bwd_bounds: the error of mag reaches its size"
+    e_inv = e_mag / (mag * (mag - e_mag)) + _r(inv)
+    e_f = 2 * e_inv + 2 * inv * e_inv + _r(inv * inv) + _r(f)
+    e_df = 4 * inv * e_inv + _r(2 * inv * inv) + 6 * inv * inv * e_inv + 2 * _r(2 * inv ** 3) + _r(df)
+    g4, e_g4 = st["g4"], e_g / 4
+    t = st["t"]
+    e_dot = (a(g4) * e_u + a(st["u"]) * e_g4 + e_u * e_g4 + _r(t)).sum(1) + 2 * U * a(t).sum(1)
+    dot = st["dot"]
+    e_term = a(dot) * e_df + a(df) * e_dot + e_df * e_dot + _r(st["term"])
+    fg = f[:, None] * g4
+    e_gu = a(g4) * e_f[:, None] + a(f)[:, None] * e_g4 + e_f[:, None] * e_g4 + _r(fg)
+    onk = np.arange(3)[None, :] == k
+    e_gu = e_gu + np.where(onk, e_term[:, None] + _r(st["gu"]), 0.0)
+    e_gu = np.where(ge1[:, None], e_gu, e_g4)
+    e_out = 2 * e_gu / w + 2 * _r(out)
+    return np.where(inside, UPDATE_SLACK * e_out, 0.0)
+
+
+def flow_warp_bwd_bounds(st: dict) -> np.ndarray:
+    """Absolute bound [n, 6] on emer_flow_warp_bwd's dflow from ``restate_flow_warp_bwd``'s values: each half is the
+    contraction gradient at q = fl(p + fl(flow noise)) (the product 1, the sum 1: the e_p of contract_bwd_bounds) of
+    g = fl(dx3 + dx2) (1 when both consumers are present, else exact), times the noise (1)."""
+    halves = []
+    for h in st["halves"]:
+        nz = np.abs(st["noise"])[:, None]
+        e = contract_bwd_bounds(h) / UPDATE_SLACK
+        halves.append(UPDATE_SLACK * (nz * e + np.where(e > 0, _r(h["out"] * st["noise"][:, None]), 0.0)))
+    return np.concatenate(halves, 1)

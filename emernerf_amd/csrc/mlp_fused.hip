@@ -36,12 +36,13 @@
 // (rb = hray W_h^T + b, an 8192-row GEMM instead of a 1M-row one) and the per-sample GEMMs shrink from K = 113 / 177
 // to K = 64 / 128.  In the backward the kernel reduces dPre0 / dPre1 over the samples of each ray, which is all the
 // per-ray operands need (dhray, dW_h and the biases are tiny per-ray GEMMs on those sums).
+#include <type_traits>
+
 #include "common.h"
 #include "bf16x3.h"
 
 namespace emer {
 
-constexpr int kFThreads = 384;  // rgb head: 6 waves; two workgroups per CU = 3 waves per SIMD = 170 VGPRs each
 constexpr int kNThreads = 512;  // neck: 8 waves; two workgroups per CU = 4 waves per SIMD = 128 VGPRs each
 constexpr int kNeckChunk = 8;  // consecutive 16-row tiles a wave processes per work item
 
@@ -177,94 +178,72 @@ __device__ __forceinline__ void st_rm(float *rowp, bool ok, int g, const f32x4 (
     for (int p = 0; p < NT; ++p) *reinterpret_cast<f32x4 *>(rowp + p * 16 + 4 * g) = v[p];
 }
 
-// level-major grid encoding [L][n_total][F]: feature k = level * F + f
-template <int KT, int F>
-__device__ __forceinline__ void ld_lm(const float *enc, int64_t n_total, int n_levels, int64_t row, bool ok, int g, f32x4 (&v)[KT]) {
+// level-major grid encoding [L][n_total][F]: feature k = level * F + f.  Tile t of a row in chain layout (lane (m, g): features
+// 16 t + 4 g .. + 3) is N pieces of W consecutive floats: piece j lies in level `level(t, g, j)` at float `sub(g)` of the level's F
+template <int F>
+struct LmPiece {
+    static_assert(F == 1 || F == 2 || F == 4 || F == 8, "level-major encodings have 1, 2, 4 or 8 features per level");
+    static constexpr int W = F < 4 ? F : 4, N = 4 / W;
+    static __device__ __forceinline__ int level(int t, int g, int j) { return F == 8 ? 2 * t + (g >> 1) : (16 / F) * t + (4 / F) * g + j; }
+    template <class Idx> static __device__ __forceinline__ Idx sub(int g) { return F == 8 ? (Idx)4 * (Idx)(g & 1) : (Idx)0; }
+};
+// The load and the store on it.  Idx = int64_t: `base` is the tensor, `row` the lane's row.  Idx = unsigned: `base` is wave-uniform (the
+// tile's first row: enc + row0 * F) and `row` the lane's row inside the tile, a 32-bit offset (needs n_total * n_levels * F < 2^30: host check).
+template <int KT, int F, class Idx>
+__device__ __forceinline__ void ld_lm_as(const float *base, Idx n_total, int n_levels, Idx row, bool ok, int g, f32x4 (&v)[KT]) {
+    using P = LmPiece<F>;
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
         v[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (F == 1) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int lv = 16 * t + 4 * g + i;
-                if (ok && lv < n_levels) v[t][i] = enc[(int64_t)lv * n_total + row];
-            }
-        } else if (F == 2) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int lv = 8 * t + 2 * g + j;
-                if (ok && lv < n_levels) {
-                    const float2 x = *reinterpret_cast<const float2 *>(enc + ((int64_t)lv * n_total + row) * 2);
+        for (int j = 0; j < P::N; ++j) {
+            const int lv = P::level(t, g, j);
+            if (ok && lv < n_levels) {
+                const float *p = base + ((Idx)lv * n_total + row) * (Idx)F + P::template sub<Idx>(g);
+                if constexpr (P::W == 1) {
+                    v[t][j] = *p;
+                } else if constexpr (P::W == 2) {
+                    const float2 x = *reinterpret_cast<const float2 *>(p);
                     v[t][2 * j] = x.x; v[t][2 * j + 1] = x.y;
+                } else {
+                    v[t] = *reinterpret_cast<const f32x4 *>(p);
                 }
             }
-        } else if (F == 4) {
-            const int lv = 4 * t + g;
-            if (ok && lv < n_levels) v[t] = *reinterpret_cast<const f32x4 *>(enc + ((int64_t)lv * n_total + row) * 4);
-        } else {  // F == 8
-            const int lv = 2 * t + (g >> 1);
-            if (ok && lv < n_levels) v[t] = *reinterpret_cast<const f32x4 *>(enc + ((int64_t)lv * n_total + row) * 8 + 4 * (g & 1));
         }
     }
 }
-template <int KT, int F>
-__device__ __forceinline__ void st_lm(float *enc, int64_t n_total, int n_levels, int64_t row, bool ok, int g, const f32x4 (&v)[KT]) {
+template <int KT, int F, class Idx>
+__device__ __forceinline__ void st_lm_as(float *base, Idx n_total, int n_levels, Idx row, bool ok, int g, const f32x4 (&v)[KT]) {
+    using P = LmPiece<F>;
     if (!ok) return;
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
-        if (F == 1) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int lv = 16 * t + 4 * g + i;
-                if (lv < n_levels) enc[(int64_t)lv * n_total + row] = v[t][i];
+        for (int j = 0; j < P::N; ++j) {
+            const int lv = P::level(t, g, j);
+            if (lv < n_levels) {
+                float *p = base + ((Idx)lv * n_total + row) * (Idx)F + P::template sub<Idx>(g);
+                if constexpr (P::W == 1) *p = v[t][j];
+                else if constexpr (P::W == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[t][2 * j], v[t][2 * j + 1]);
+                else *reinterpret_cast<f32x4 *>(p) = v[t];
             }
-        } else if (F == 2) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int lv = 8 * t + 2 * g + j;
-                if (lv < n_levels) *reinterpret_cast<float2 *>(enc + ((int64_t)lv * n_total + row) * 2) = make_float2(v[t][2 * j], v[t][2 * j + 1]);
-            }
-        } else if (F == 4) {
-            const int lv = 4 * t + g;
-            if (lv < n_levels) *reinterpret_cast<f32x4 *>(enc + ((int64_t)lv * n_total + row) * 4) = v[t];
-        } else {
-            const int lv = 2 * t + (g >> 1);
-            if (lv < n_levels) *reinterpret_cast<f32x4 *>(enc + ((int64_t)lv * n_total + row) * 8 + 4 * (g & 1)) = v[t];
         }
     }
 }
-
-// The same accesses with a wave-uniform base (the tile's first row: enc + row0 * F) and 32-bit per-lane offsets: `mrow` is the
-// lane's row inside the tile.  Requires n_total * n_levels * F < 2^30 (host check).
 template <int KT, int F>
-__device__ __forceinline__ void ld_lm_t(const float *base, unsigned n_total, int n_levels, unsigned mrow, int g, f32x4 (&v)[KT]) {
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-        v[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (F == 1) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int lv = 16 * t + 4 * g + i;
-                if (lv < n_levels) v[t][i] = base[(unsigned)lv * n_total + mrow];
-            }
-        } else if (F == 2) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int lv = 8 * t + 2 * g + j;
-                if (lv < n_levels) {
-                    const float2 x = *reinterpret_cast<const float2 *>(base + ((unsigned)lv * n_total + mrow) * 2u);
-                    v[t][2 * j] = x.x; v[t][2 * j + 1] = x.y;
-                }
-            }
-        } else if (F == 4) {
-            const int lv = 4 * t + g;
-            if (lv < n_levels) v[t] = *reinterpret_cast<const f32x4 *>(base + ((unsigned)lv * n_total + mrow) * 4u);
-        } else {  // F == 8
-            const int lv = 2 * t + (g >> 1);
-            if (lv < n_levels) v[t] = *reinterpret_cast<const f32x4 *>(base + ((unsigned)lv * n_total + mrow) * 8u + 4u * (g & 1));
-        }
-    }
+__device__ __forceinline__ void ld_lm(const float *enc, int64_t n_total, int n_levels, int64_t row, bool ok, int g, f32x4 (&v)[KT]) {
+    ld_lm_as<KT, F, int64_t>(enc, n_total, n_levels, row, ok, g, v);
 }
+template <int KT, int F>
+__device__ __forceinline__ void st_lm(float *enc, int64_t n_total, int n_levels, int64_t row, bool ok, int g, const f32x4 (&v)[KT]) {
+    st_lm_as<KT, F, int64_t>(enc, n_total, n_levels, row, ok, g, v);
+}
+template <int KT, int F>   // (loads are unconditional in the row: the callers clamp it)
+__device__ __forceinline__ void ld_lm_t(const float *base, unsigned n_total, int n_levels, unsigned mrow, int g, f32x4 (&v)[KT]) {
+    ld_lm_as<KT, F, unsigned>(base, n_total, n_levels, mrow, true, g, v);
+}
+// The store with a wave-uniform base stays written out.  Twin: st_lm_as<KT, F, unsigned>, which holds every resource but moves the code of
+// neck_bwdw_kernel<1, 2, .>, and <1, 2, 2> then runs 0.3 % slower than the parent in both A/B sessions (duplicates table).
 template <int KT, int F>
 __device__ __forceinline__ void st_lm_t(float *base, unsigned n_total, int n_levels, unsigned mrow, bool ok, int g, const f32x4 (&v)[KT]) {
     if (!ok) return;
@@ -302,13 +281,53 @@ struct NeckFwdArgs {
     float *dens;  // [n] exp(feature0 - 1)
 };
 
+// ---- stages that the forward kernels share ------------------------------------------------------------------------------------------
+// trunc_exp (the reference's density activation): exp(x - 1) forward, g * exp(min(x - 1, 15)) = g * min(y, e^15) backward through the saved y
+constexpr float kTruncExpClamp = 3269017.3724721107f;   // e^15
+__device__ __forceinline__ float trunc_exp_fwd(float x) { return expf(x - 1.0f); }
+__device__ __forceinline__ float trunc_exp_bwd(float ddens, float dens) { return ddens * fminf(dens, kTruncExpClamp); }
+
+// The hidden layer every chain starts with: h = relu(W0 x + b0) from the input tile in registers (neck_fwd_kernel, field_fwd_kernel,
+// rmlp_fwd_kernel).  xo: the caller's temporary for the split input.
+template <int KT0>
+__device__ __forceinline__ void hidden_fwd(const W3 w0p, const float *b0l, const f32x4 (&x)[KT0], int g, Opd<(KT0 + 1) / 2> &xo, f32x4 (&h)[4]) {
+    make_opd<KT0>(x, xo);
+    init_bias<4>(b0l, g, h);
+    tgemm<(KT0 + 1) / 2, 4>(w0p, xo, h);
+    relu<4>(h);
+}
+
+// The density MLP's output layer 64 -> 1: sixteen fp32 FMAs per lane and a reduction over the four lane groups of the row -- no split, no
+// matrix instruction (the bf16x3 form spent 88 VALU on the split and 12 instructions on a 1-row output).  w1r: this lane's 16 weights of the
+// output row (features 16 p + 4 g + i); every lane of the row gets the sum
+__device__ __forceinline__ float dot64_row(const f32x4 (&w1r)[4], const f32x4 (&h)[4]) {
+    float dot = 0.0f;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dot = fmaf(w1r[p][i], h[p][i], dot);
+    dot += __shfl_xor(dot, 16, 64);
+    dot += __shfl_xor(dot, 32, 64);
+    return dot;
+}
+
+// LDS of neck_fwd_kernel: the kernel takes its pointers from it, the entry point the byte count (u32x4 units, then floats behind `fl`)
+template <int KT0, int NT1>
+struct NeckFwdLds {
+    static constexpr int KS0 = (KT0 + 1) / 2;
+    static constexpr int w0 = 0, w1 = w0 + w3_units(4, KS0), fl = w1 + w3_units(NT1, 2);
+    static constexpr int b0 = 0, b1 = b0 + 64, w1v = b1 + NT1 * 16, n_fl = w1v + 64;
+    static constexpr size_t bytes = (size_t)fl * 16 + n_fl * sizeof(float);
+};
+
 // NT1 = output tiles of the second layer: 4 (64 features), 8 (128 features), 1 (density only: 1 feature -> trunc_exp)
 template <int KT0, int F, int NT1>
 __global__ __launch_bounds__(kNThreads, 4) void neck_fwd_kernel(const NeckFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    constexpr int KS0 = (KT0 + 1) / 2;
-    u32x4 *w0l = smem, *w1l = w0l + w3_units(4, KS0);
-    float *b0l = reinterpret_cast<float *>(w1l + w3_units(NT1, 2)), *b1l = b0l + 64, *w1v = b1l + NT1 * 16;
+    using Lds = NeckFwdLds<KT0, NT1>;
+    constexpr int KS0 = Lds::KS0;
+    u32x4 *w0l = smem + Lds::w0, *w1l = smem + Lds::w1;
+    float *fl = reinterpret_cast<float *>(smem + Lds::fl), *b0l = fl + Lds::b0, *b1l = fl + Lds::b1, *w1v = fl + Lds::w1v;
     stage_w3(w0l, 4, KS0, a.w0);
     if constexpr (NT1 == 1) {   // density MLP: the single output row stays fp32 (a 64-term dot product per row on the VALU)
         for (int i = threadIdx.x; i < 64; i += (int)blockDim.x) w1v[i] = a.w1.w[i * a.w1.sk];
@@ -325,6 +344,8 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_fwd_kernel(const NeckFwdArg
 #pragma unroll
         for (int p = 0; p < 4; ++p) w1r[p] = *reinterpret_cast<const f32x4 *>(w1v + 16 * p + 4 * g);
     }
+    // The chunked tile loop with the input fetched one tile ahead.  Twin: rmlp_fwd_kernel's loop; written out in both because one
+    // chunk_loop(load, body) template cost registers and scratch here (duplicates table).
     const int64_t n_tiles = (a.n + 15) >> 4, n_chunks = (n_tiles + kNeckChunk - 1) / kNeckChunk;
     for (int64_t c = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave; c < n_chunks; c += (int64_t)gridDim.x * (blockDim.x >> 6)) {
         const int64_t t0 = c * kNeckChunk;
@@ -338,23 +359,12 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_fwd_kernel(const NeckFwdArg
             for (int t = 0; t < KT0; ++t) x[t] = xn[t];
             if (j + 1 < kNeckChunk && t0 + j + 1 < n_tiles) ld_lm<KT0, F>(a.enc, a.n, a.n_levels, row + 16, row + 16 < a.n, g, xn);
             Opd<KS0> xo;
-            make_opd<KT0>(x, xo);
             f32x4 h[4];
-            init_bias<4>(b0l, g, h);
-            tgemm<KS0, 4>(w0p, xo, h);
-            relu<4>(h);
+            hidden_fwd<KT0>(w0p, b0l, x, g, xo, h);
             if (a.h1) st_rm<4>(a.h1 + row * 64, ok, g, h);
             if constexpr (NT1 == 1) {
-                // 64 -> 1: sixteen fp32 FMAs per lane and a reduction over the four lane groups of the row -- no split, no
-                // matrix instruction (the bf16x3 form spent 88 VALU on the split and 12 instructions on a 1-row output)
-                float dot = 0.0f;
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) dot = fmaf(w1r[p][i], h[p][i], dot);
-                dot += __shfl_xor(dot, 16, 64);
-                dot += __shfl_xor(dot, 32, 64);
-                if (ok && g == 0) a.dens[row] = expf(dot + b1l[0] - 1.0f);
+                const float dot = dot64_row(w1r, h);
+                if (ok && g == 0) a.dens[row] = trunc_exp_fwd(dot + b1l[0]);
             } else {
                 Opd<2> ho;
                 make_opd<4>(h, ho);
@@ -363,7 +373,7 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_fwd_kernel(const NeckFwdArg
                 init_bias<4>(b1l, g, o);
                 tgemm<2, 4>(w1p, ho, o);
                 st_rm<4>(a.out0 + row * 64, ok, g, o);
-                if (a.dens && ok && g == 0) a.dens[row] = expf(o[0][0] - 1.0f);
+                if (a.dens && ok && g == 0) a.dens[row] = trunc_exp_fwd(o[0][0]);
                 if constexpr (NT1 == 8) {
                     init_bias<4>(b1l + 64, g, o);
                     tgemm<2, 4>(w3_tile(w1p, 4), ho, o);
@@ -426,14 +436,8 @@ __global__ __launch_bounds__(kNThreads, 4) void density_fwd_kernel(const NeckFwd
                 for (int p = 0; p < 4; ++p) h[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[p][s], x[j][s], h[p], 0, 0, 0);
             relu<4>(h);
             if (a.h1) st_rm<4>(a.h1 + row * 64, ok, g, h);
-            float dot = 0.0f;
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) dot = fmaf(w1r[p][i], h[p][i], dot);
-            dot += __shfl_xor(dot, 16, 64);
-            dot += __shfl_xor(dot, 32, 64);
-            if (ok && g == 0) a.dens[row] = expf(dot + b1 - 1.0f);
+            const float dot = dot64_row(w1r, h);
+            if (ok && g == 0) a.dens[row] = trunc_exp_fwd(dot + b1);
         }
     }
 }
@@ -453,14 +457,32 @@ struct NeckBwdArgs {
     float *denc;         // level-major [L][n][F]
 };
 
+// The input gradient every data-gradient chain ends with (neck_bwd_kernel, rmlp_bwd_kernel): de = W0^T dpre0 from the masked gradient da.
+// (dao: the caller's temporary, like xo of hidden_fwd -- declared inside, both functions move their callers' register allocation.)
+template <int KT0>
+__device__ __forceinline__ void input_grad(const W3 w0tp, const f32x4 (&da)[4], Opd<2> &dao, f32x4 (&de)[KT0]) {
+    make_opd<4>(da, dao);
+    zero<KT0>(de);
+    tgemm<2, KT0>(w0tp, dao, de);
+}
+
+// LDS of neck_bwd_kernel (u32x4 units; density mode keeps W1's single row as 64 floats at w1)
+template <int KT0, int KT1>
+struct NeckBwdLds {
+    static_assert(KT1 == 0 || KT1 == 4 || KT1 == 8, "neck_bwd: 0, 64 or 128 gradient columns");
+    static constexpr int KS1 = KT1 / 2;  // k-steps of the transposed second layer (0: density mode, W1 is one fp32 row)
+    static constexpr int w0 = 0, w1 = w0 + w3_units(KT0, 2);
+    static constexpr size_t bytes = (size_t)(w1 + (KT1 == 0 ? 0 : w3_units(4, KS1))) * 16 + (KT1 == 0 ? 64 * sizeof(float) : 0);
+};
+
 // KT1 = input tiles of the transposed second layer: 4 / 8 (neck), 0 (density mode: rank-1, no MFMA)
 template <int KT0, int F, int KT1>
 __global__ __launch_bounds__(kNThreads, 4) void neck_bwd_kernel(const NeckBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    constexpr int KS1 = KT1 / 2;  // k-steps of the transposed second layer (0: density mode, W1 is one fp32 row)
+    using Lds = NeckBwdLds<KT0, KT1>;
+    constexpr int KS1 = Lds::KS1;
     constexpr int KS1e = KS1 > 0 ? KS1 : 1;
-    static_assert(KT1 == 0 || KT1 == 4 || KT1 == 8, "neck_bwd: 0, 64 or 128 gradient columns");
-    u32x4 *w0l = smem, *w1l = w0l + w3_units(KT0, 2);
+    u32x4 *w0l = smem + Lds::w0, *w1l = smem + Lds::w1;
     float *w1v = reinterpret_cast<float *>(w1l);  // density mode: W1[0][0..63]
     stage_w3(w0l, KT0, 2, a.w0t);
     if constexpr (KT1 == 0) {
@@ -480,7 +502,7 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_bwd_kernel(const NeckBwdArg
             f32x4 mk[4];
             ld_rm<4>(a.h1 + row * 64, ok, g, mk);
             float fix = 0.0f;
-            if (a.ddens && ok) fix = a.ddens[row] * fminf(a.dens[row], 3269017.3724721107f);
+            if (a.ddens && ok) fix = trunc_exp_bwd(a.ddens[row], a.dens[row]);
             f32x4 da[4];
             if constexpr (KT1 == 0) {
                 // rank-1: dA[n] = W1[0][n] * dPre1
@@ -511,13 +533,11 @@ __global__ __launch_bounds__(kNThreads, 4) void neck_bwd_kernel(const NeckBwdArg
                     tgemm<2, 4>(W3{w1p.p + 2 * 64, w1p.ks, w1p.plane}, dop, da);  // k-steps 2, 3
                 }
             }
-            relu_mask<4>(da, mk);
+            relu_mask<4>(da, mk);   // (twin of these two lines: rmlp_bwd_kernel; as a function they move the code of 31 instantiations)
             st_rm<4>(a.dpre0 + row * 64, ok, g, da);
             Opd<2> dao;
-            make_opd<4>(da, dao);
             f32x4 de[KT0];
-            zero<KT0>(de);
-            tgemm<2, KT0>(w0p, dao, de);
+            input_grad<KT0>(w0p, da, dao, de);
             st_lm<KT0, F>(a.denc, a.n, a.n_levels, row, ok, g, de);
         }
     }
@@ -751,7 +771,7 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
         {
             const int64_t row = tile * 16 + m;
             const bool ok = row < a.n;
-            const float fix = ok ? cur.dd * fminf(cur.de, 3269017.3724721107f) : 0.0f;
+            const float fix = ok ? trunc_exp_bwd(cur.dd, cur.de) : 0.0f;
             // enc tile -> operand of dW0 (xs) and, through the first layer, h1: operand of dW1 (hs) and relu'(h1) as 16 bits
             SwP hq[2];   // h1 features 0-31, 32-63 with the rows on the reduction index
             unsigned relu_bits = 0u;
@@ -882,18 +902,71 @@ struct RgbFwdArgs {
     float *out;                        // [n][3]
 };
 
+// LDS of the rgb head's forward: W0g | W1a | W1g (64 x 64 each) | W2 (u32x4 units from the block's base; rgb_fwd_kernel: smem, field_fwd_kernel:
+// behind the neck's weights), and b2 padded to 16 floats
+struct RgbFwdLds {
+    static constexpr int w0 = 0, w1a = w0 + w3_units(4, 2), w1g = w1a + w3_units(4, 2), w2 = w1g + w3_units(4, 2), units = w2 + w3_units(1, 2);
+    static constexpr int n_b2 = 16;
+    static constexpr size_t bytes = (size_t)units * 16 + n_b2 * sizeof(float);
+};
+struct RgbFwdW { W3 w0, w1a, w1g, w2; const float *b2; };   // this lane's view of them
+__device__ __forceinline__ void rgb_fwd_stage(u32x4 *base, const RgbFwdArgs &a) {
+    stage_w3(base + RgbFwdLds::w0, 4, 2, a.w0g);
+    stage_w3(base + RgbFwdLds::w1a, 4, 2, a.w1a);
+    stage_w3(base + RgbFwdLds::w1g, 4, 2, a.w1g);
+    stage_w3(base + RgbFwdLds::w2, 1, 2, a.w2);
+}
+__device__ __forceinline__ RgbFwdW rgb_fwd_weights(const u32x4 *base, const float *b2l, int lane) {
+    return RgbFwdW{w3_at(base + RgbFwdLds::w0, 4, 2, lane), w3_at(base + RgbFwdLds::w1a, 4, 2, lane), w3_at(base + RgbFwdLds::w1g, 4, 2, lane),
+                   w3_at(base + RgbFwdLds::w2, 1, 2, lane), b2l};
+}
+
+// The rgb head's forward on tile j of a ray, from the geometry features in registers (x) to the colour store (rgb_fwd_kernel,
+// field_fwd_kernel): a1 = relu(W0g x + rb0), a2 = relu(W1g x + W1a a1 + rb1), out = sigmoid(W2 a2 + b2).  rb0 / rb1: the ray's
+// pre-activations at this lane's columns (+ 4 g); a1 / a2 / outp: the ray's first row (a1 / a2 stored only with keep / keep2: 2/3 of the bytes).
+// Twin, written out around its hand-placed stages: the recomputation of a1 / a2 in rgb_bwdwr_kernel.
+__device__ __forceinline__ void rgb_fwd_tile(const RgbFwdW &w, const f32x4 (&x)[4], const float *rb0, const float *rb1, float *a1, float *a2, float *outp,
+                                             bool keep, bool keep2, unsigned lo64, int j, int m, int g) {
+    Opd<2> xo;
+    make_opd<4>(x, xo);
+    f32x4 h[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) h[p] = *reinterpret_cast<const f32x4 *>(rb0 + 16 * p);
+    tgemm<2, 4, false>(w.w0, xo, h);
+    relu<4>(h);
+    if (keep)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a1 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h[p];
+    f32x4 h2[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) h2[p] = *reinterpret_cast<const f32x4 *>(rb1 + 16 * p);
+    tgemm<2, 4, false>(w.w1g, xo, h2);   // geo part first: its operand dies here
+    Opd<2> ho;
+    make_opd<4>(h, ho);
+    tgemm<2, 4, false>(w.w1a, ho, h2);
+    relu<4>(h2);
+    if (keep2)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a2 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h2[p];
+    make_opd<4>(h2, ho);
+    f32x4 o[1];
+    init_bias<1>(w.b2, g, o);
+    tgemm<2, 1>(w.w2, ho, o);
+    if (g == 0) {
+        float *op = outp + ((unsigned)j * 48u + 3u * m);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) op[i] = 1.0f / (1.0f + expf(-o[0][i]));
+    }
+}
+
 __global__ __launch_bounds__(kNThreads, 4) void rgb_fwd_kernel(const RgbFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    u32x4 *w0l = smem, *w1al = w0l + w3_units(4, 2), *w1gl = w1al + w3_units(4, 2), *w2l = w1gl + w3_units(4, 2);
-    float *b2l = reinterpret_cast<float *>(w2l + w3_units(1, 2));
-    stage_w3(w0l, 4, 2, a.w0g);
-    stage_w3(w1al, 4, 2, a.w1a);
-    stage_w3(w1gl, 4, 2, a.w1g);
-    stage_w3(w2l, 1, 2, a.w2);
-    stage_b(b2l, 16, a.b2, a.w2.n);
+    float *b2l = reinterpret_cast<float *>(smem + RgbFwdLds::units);
+    rgb_fwd_stage(smem, a);
+    stage_b(b2l, RgbFwdLds::n_b2, a.b2, a.w2.n);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
-    const W3 w0p = w3_at(w0l, 4, 2, lane), w1ap = w3_at(w1al, 4, 2, lane), w1gp = w3_at(w1gl, 4, 2, lane), w2p = w3_at(w2l, 1, 2, lane);
+    const RgbFwdW w = rgb_fwd_weights(smem, b2l, lane);
     const int tpr = a.tiles_per_ray;
     // Addressing: the ray is wave-uniform, so every tensor gets ONE scalar base per ray and the lanes share 32-bit
     // offsets (SGPR base + VGPR offset loads / stores) instead of a 64-bit pointer pair per tensor.
@@ -910,44 +983,15 @@ __global__ __launch_bounds__(kNThreads, 4) void rgb_fwd_kernel(const RgbFwdArgs 
             f32x4 x[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) x[p] = *reinterpret_cast<const f32x4 *>(geo + (log + (unsigned)j * 16u * (unsigned)a.ld_geo + 16u * p));
-            Opd<2> xo;
-            make_opd<4>(x, xo);
-            f32x4 h[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) h[p] = *reinterpret_cast<const f32x4 *>(rb0 + 16 * p);
-            tgemm<2, 4, false>(w0p, xo, h);
-            relu<4>(h);
-            if (keep)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a1 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h[p];
-            f32x4 h2[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) h2[p] = *reinterpret_cast<const f32x4 *>(rb1 + 16 * p);
-            tgemm<2, 4, false>(w1gp, xo, h2);   // geo part first: its operand dies here
-            Opd<2> ho;
-            make_opd<4>(h, ho);
-            tgemm<2, 4, false>(w1ap, ho, h2);
-            relu<4>(h2);
-            if (keep2)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a2 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h2[p];
-            make_opd<4>(h2, ho);
-            f32x4 o[1];
-            init_bias<1>(b2l, g, o);
-            tgemm<2, 1>(w2p, ho, o);
-            if (g == 0) {
-                float *op = outp + ((unsigned)j * 48u + 3u * m);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) op[i] = 1.0f / (1.0f + expf(-o[0][i]));
-            }
+            rgb_fwd_tile(w, x, rb0, rb1, a1, a2, outp, keep, keep2, lo64, j, m, g);
         }
     }
 }
 
 // ------------------------------------------------------------------------------ neck + rgb head in one forward kernel
 // The static field of a colour query: level-major grid encoding -> neck (geometry features, density) -> rgb head, a wave
-// keeping its 16 rows in registers from the encoding to the colour.  Same arithmetic, instruction for instruction, as
-// neck_fwd_kernel followed by rgb_fwd_kernel; what it saves is the rgb head's read of the 256 B / sample geometry features
+// keeping its 16 rows in registers from the encoding to the colour.  The same stages as neck_fwd_kernel followed by rgb_fwd_kernel
+// (hidden_fwd, rgb_fwd_tile), so bitwise their results; what it saves is the rgb head's read of the 256 B / sample geometry features
 // (they are still WRITTEN once: the backward needs them) and a launch.  The weights of both stages (114-126 KB) leave room for
 // one workgroup per CU, so the workgroup is 1024 lanes = the same four waves per SIMD as the separate kernels.
 constexpr int kFieldThreads = 1024;
@@ -959,26 +1003,32 @@ struct FieldFwdArgs {
     RgbFwdArgs r;                                    // the rgb head (r.geo / r.ld_geo unused)
 };
 
+// LDS of field_fwd_kernel: the neck's two matrices, the rgb head's block (RgbFwdLds), then the biases as floats behind `fl`
+template <int KT0>
+struct FieldFwdLds {
+    static constexpr int KS0 = (KT0 + 1) / 2;
+    static constexpr int nw0 = 0, nw1 = nw0 + w3_units(4, KS0), rgb = nw1 + w3_units(4, 2), fl = rgb + RgbFwdLds::units;
+    static constexpr int nb0 = 0, nb1 = nb0 + 64, b2 = nb1 + 64, n_fl = b2 + RgbFwdLds::n_b2;
+    static constexpr size_t bytes = (size_t)fl * 16 + n_fl * sizeof(float);
+};
+
 template <int KT0, int F>
 __global__ __launch_bounds__(kFieldThreads) void field_fwd_kernel(const FieldFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    constexpr int KS0 = (KT0 + 1) / 2;
-    u32x4 *nw0l = smem, *nw1l = nw0l + w3_units(4, KS0), *w0l = nw1l + w3_units(4, 2), *w1al = w0l + w3_units(4, 2),
-          *w1gl = w1al + w3_units(4, 2), *w2l = w1gl + w3_units(4, 2);
-    float *nb0l = reinterpret_cast<float *>(w2l + w3_units(1, 2)), *nb1l = nb0l + 64, *b2l = nb1l + 64;
+    using Lds = FieldFwdLds<KT0>;
+    constexpr int KS0 = Lds::KS0;
+    u32x4 *nw0l = smem + Lds::nw0, *nw1l = smem + Lds::nw1;
+    float *fl = reinterpret_cast<float *>(smem + Lds::fl), *nb0l = fl + Lds::nb0, *nb1l = fl + Lds::nb1, *b2l = fl + Lds::b2;
     stage_w3(nw0l, 4, KS0, a.nw0);
     stage_w3(nw1l, 4, 2, a.nw1);
-    stage_w3(w0l, 4, 2, a.r.w0g);
-    stage_w3(w1al, 4, 2, a.r.w1a);
-    stage_w3(w1gl, 4, 2, a.r.w1g);
-    stage_w3(w2l, 1, 2, a.r.w2);
+    rgb_fwd_stage(smem + Lds::rgb, a.r);
     stage_b(nb0l, 64, a.nb0, a.nw0.n);
     stage_b(nb1l, 64, a.nb1, a.nw1.n);
-    stage_b(b2l, 16, a.r.b2, a.r.w2.n);
+    stage_b(b2l, RgbFwdLds::n_b2, a.r.b2, a.r.w2.n);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
     const W3 nw0p = w3_at(nw0l, 4, KS0, lane), nw1p = w3_at(nw1l, 4, 2, lane);
-    const W3 w0p = w3_at(w0l, 4, 2, lane), w1ap = w3_at(w1al, 4, 2, lane), w1gp = w3_at(w1gl, 4, 2, lane), w2p = w3_at(w2l, 1, 2, lane);
+    const RgbFwdW w = rgb_fwd_weights(smem + Lds::rgb, b2l, lane);
     const int tpr = a.r.tiles_per_ray;
     const unsigned lo64 = (unsigned)(m * 64 + 4 * g);
     const bool keep = a.r.a1 != nullptr, keep2 = a.r.a2 != nullptr;   // [r6] a2 (or both) may be left to a recomputing backward
@@ -993,11 +1043,8 @@ __global__ __launch_bounds__(kFieldThreads) void field_fwd_kernel(const FieldFwd
                 f32x4 e[KT0];
                 ld_lm_t<KT0, F>(encp + (unsigned)j * 16u * (unsigned)F, (unsigned)a.n, a.n_levels, (unsigned)m, g, e);
                 Opd<KS0> eo;
-                make_opd<KT0>(e, eo);
                 f32x4 hn[4];
-                init_bias<4>(nb0l, g, hn);
-                tgemm<KS0, 4>(nw0p, eo, hn);
-                relu<4>(hn);
+                hidden_fwd<KT0>(nw0p, nb0l, e, g, eo, hn);
                 Opd<2> hno;
                 make_opd<4>(hn, hno);
                 init_bias<4>(nb1l, g, x);
@@ -1005,38 +1052,8 @@ __global__ __launch_bounds__(kFieldThreads) void field_fwd_kernel(const FieldFwd
             }
 #pragma unroll
             for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(geo + (lo64 + (unsigned)j * 1024u + 16u * p)) = x[p];
-            if (g == 0) dens[(unsigned)j * 16u + (unsigned)m] = expf(x[0][0] - 1.0f);
-            // rgb head (rgb_fwd_kernel's tile body)
-            Opd<2> xo;
-            make_opd<4>(x, xo);
-            f32x4 h[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) h[p] = *reinterpret_cast<const f32x4 *>(rb0 + 16 * p);
-            tgemm<2, 4, false>(w0p, xo, h);
-            relu<4>(h);
-            if (keep)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a1 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h[p];
-            f32x4 h2[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) h2[p] = *reinterpret_cast<const f32x4 *>(rb1 + 16 * p);
-            tgemm<2, 4, false>(w1gp, xo, h2);
-            Opd<2> ho;
-            make_opd<4>(h, ho);
-            tgemm<2, 4, false>(w1ap, ho, h2);
-            relu<4>(h2);
-            if (keep2)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(a2 + (lo64 + (unsigned)j * 1024u + 16u * p)) = h2[p];
-            make_opd<4>(h2, ho);
-            f32x4 o[1];
-            init_bias<1>(b2l, g, o);
-            tgemm<2, 1>(w2p, ho, o);
-            if (g == 0) {
-                float *op = outp + ((unsigned)j * 48u + 3u * m);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) op[i] = 1.0f / (1.0f + expf(-o[0][i]));
-            }
+            if (g == 0) dens[(unsigned)j * 16u + (unsigned)m] = trunc_exp_fwd(x[0][0]);
+            rgb_fwd_tile(w, x, rb0, rb1, a1, a2, outp, keep, keep2, lo64, j, m, g);
         }
     }
 }
@@ -1084,9 +1101,15 @@ __device__ __forceinline__ float row16_reduce_scatter(const f32x4 (&e)[4], float
     return (b0 ? r3[1] : r3[0]) + dpp_mov<0xB1>(b0 ? r3[0] : r3[1]);
 }
 
+// LDS of rgb_bwd_kernel (u32x4 units): W1a^T | W1g^T | W0g^T
+struct RgbBwdLds {
+    static constexpr int w1a = 0, w1g = w1a + w3_units(4, 2), w0 = w1g + w3_units(4, 2);
+    static constexpr size_t bytes = (size_t)(w0 + w3_units(4, 2)) * 16;
+};
+
 __global__ __launch_bounds__(kNThreads, 4) void rgb_bwd_kernel(const RgbBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    u32x4 *w1al = smem, *w1gl = w1al + w3_units(4, 2), *w0l = w1gl + w3_units(4, 2);
+    u32x4 *w1al = smem + RgbBwdLds::w1a, *w1gl = smem + RgbBwdLds::w1g, *w0l = smem + RgbBwdLds::w0;
     stage_w3(w1al, 4, 2, a.w1at);
     stage_w3(w1gl, 4, 2, a.w1gt);
     stage_w3(w0l, 4, 2, a.w0gt);
@@ -1620,7 +1643,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
                 // (a clamped repeat of the last tile re-reads with j != 0 unless tpr == 1: then it reloads its own ray into the other buffer, harmless)
             }
             // ---- recomputation: a1 = relu(W0g x + rb0), a2 = relu(W1g x + W1a a1 + rb1).  Eight stages on x (k-step 0 of all four
-            // accumulator pairs first, so that the split of k-step 1 runs next to them), four on a1.
+            // accumulator pairs first, so that the split of k-step 1 runs next to them), four on a1.  Twin: rgb_fwd_tile (the forward's form).
             Opd<2> xo, ho;
             SwP Bq[4];   // a1 features 0-31, 32-63; geo features 0-31, 32-63 (rows on the reduction index, 32-feature blocks)
             if constexpr (A1_STORED) {
@@ -1791,7 +1814,7 @@ __global__ __launch_bounds__(kNThreads, 2) void density_bwdw_kernel(const DensBw
 #pragma unroll
                 for (int p = 0; p < 4; ++p) h[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[p][s], x[j][s], h[p], 0, 0, 0);
             relu<4>(h);
-            const float fix = ok ? dd[j] * fminf(de[j], 3269017.3724721107f) : 0.0f;  // trunc_exp': d(pre-activation of the output)
+            const float fix = ok ? trunc_exp_bwd(dd[j], de[j]) : 0.0f;  // d(pre-activation of the output)
             f32x4 dh[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p)
@@ -1885,12 +1908,22 @@ __device__ __forceinline__ void st_narrow(float *rowp, bool ok, int g, int n_val
             if (16 * p + 4 * g + i < n_valid) rowp[16 * p + 4 * g + i] = v[p][i];
 }
 
+// LDS of rmlp_fwd_kernel (u32x4 units, then floats behind `fl`)
+template <int KT0, int NL, int NTO>
+struct RMlpFwdLds {
+    static constexpr int KS0 = (KT0 + 1) / 2, NP1 = NL == 3 ? 4 : NTO;
+    static constexpr int w0 = 0, w1 = w0 + w3_units(4, KS0), w2 = w1 + w3_units(NP1, 2), fl = w2 + (NL == 3 ? w3_units(NTO, 2) : 0);
+    static constexpr int b0 = 0, b1 = b0 + 64, b2 = b1 + 64, n_fl = b2 + 64;
+    static constexpr size_t bytes = (size_t)fl * 16 + n_fl * sizeof(float);
+};
+
 template <int KT0, int F, int NL, int NTO>
 __global__ __launch_bounds__(kNThreads, 4) void rmlp_fwd_kernel(const RMlpFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    constexpr int KS0 = (KT0 + 1) / 2, NP1 = NL == 3 ? 4 : NTO;
-    u32x4 *w0l = smem, *w1l = w0l + w3_units(4, KS0), *w2l = w1l + w3_units(NP1, 2);
-    float *b0l = reinterpret_cast<float *>(w2l + (NL == 3 ? w3_units(NTO, 2) : 0)), *b1l = b0l + 64, *b2l = b1l + 64;
+    using Lds = RMlpFwdLds<KT0, NL, NTO>;
+    constexpr int KS0 = Lds::KS0, NP1 = Lds::NP1;
+    u32x4 *w0l = smem + Lds::w0, *w1l = smem + Lds::w1, *w2l = smem + Lds::w2;
+    float *fl = reinterpret_cast<float *>(smem + Lds::fl), *b0l = fl + Lds::b0, *b1l = fl + Lds::b1, *b2l = fl + Lds::b2;
     stage_w3(w0l, 4, KS0, a.w0);
     stage_w3(w1l, NP1, 2, a.w1);
     if (NL == 3) stage_w3(w2l, NTO, 2, a.w2);
@@ -1901,11 +1934,12 @@ __global__ __launch_bounds__(kNThreads, 4) void rmlp_fwd_kernel(const RMlpFwdArg
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
     const W3 w0p = w3_at(w0l, 4, KS0, lane), w1p = w3_at(w1l, NP1, 2, lane), w2p = w3_at(w2l, NTO, 2, lane);
     const bool wide_out = (a.n_out & 3) == 0 && (a.ldo & 3) == 0;
-    const int64_t n_tiles = (a.n + 15) >> 4, n_chunks = (n_tiles + kNeckChunk - 1) / kNeckChunk;
     auto load_x = [&](int64_t row, f32x4 (&v)[KT0]) {
         if constexpr (F == 0) ld_rm_k<KT0>(a.x + row * a.ldx, row < a.n, g, a.k0, v);
         else ld_lm<KT0, F>(a.x, a.n, a.n_levels, row, row < a.n, g, v);
     };
+    // (twin of neck_fwd_kernel's chunked tile loop: see there)
+    const int64_t n_tiles = (a.n + 15) >> 4, n_chunks = (n_tiles + kNeckChunk - 1) / kNeckChunk;
     for (int64_t c = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave; c < n_chunks; c += (int64_t)gridDim.x * (blockDim.x >> 6)) {
         const int64_t t0 = c * kNeckChunk;
         f32x4 xn[KT0];
@@ -1918,11 +1952,8 @@ __global__ __launch_bounds__(kNThreads, 4) void rmlp_fwd_kernel(const RMlpFwdArg
             for (int t = 0; t < KT0; ++t) x[t] = xn[t];
             if (j + 1 < kNeckChunk && t0 + j + 1 < n_tiles) load_x(row + 16, xn);
             Opd<KS0> xo;
-            make_opd<KT0>(x, xo);
             f32x4 h[4];
-            init_bias<4>(b0l, g, h);
-            tgemm<KS0, 4>(w0p, xo, h);
-            relu<4>(h);
+            hidden_fwd<KT0>(w0p, b0l, x, g, xo, h);
             if (a.h1) st_rm<4>(a.h1 + row * 64, ok, g, h);
             Opd<2> ho;
             make_opd<4>(h, ho);
@@ -1958,11 +1989,20 @@ struct RMlpBwdArgs {
     float *dx; int64_t lddx;           // gradient of the input: row-major [n][lddx] or level-major; null: not needed
 };
 
+// LDS of rmlp_bwd_kernel (u32x4 units)
+template <int KT0, int NL, int NTO>
+struct RMlpBwdLds {
+    static constexpr int KSL = (NTO + 1) / 2;
+    static constexpr int wl = 0, w1 = wl + w3_units(4, KSL), w0 = w1 + (NL == 3 ? w3_units(4, 2) : 0);
+    static constexpr size_t bytes = (size_t)(w0 + w3_units(KT0, 2)) * 16;
+};
+
 template <int KT0, int F, int NL, int NTO>
 __global__ __launch_bounds__(kNThreads, 4) void rmlp_bwd_kernel(const RMlpBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-    constexpr int KSL = (NTO + 1) / 2;
-    u32x4 *wll = smem, *w1l = wll + w3_units(4, KSL), *w0l = w1l + (NL == 3 ? w3_units(4, 2) : 0);
+    using Lds = RMlpBwdLds<KT0, NL, NTO>;
+    constexpr int KSL = Lds::KSL;
+    u32x4 *wll = smem + Lds::wl, *w1l = smem + Lds::w1, *w0l = smem + Lds::w0;
     stage_w3(wll, 4, KSL, a.wlt);
     if (NL == 3) stage_w3(w1l, 4, 2, a.w1t);
     stage_w3(w0l, KT0, 2, a.w0t);
@@ -1997,14 +2037,12 @@ __global__ __launch_bounds__(kNThreads, 4) void rmlp_bwd_kernel(const RMlpBwdArg
         }
         f32x4 mk1[4];
         ld_rm<4>(a.h1 + row * 64, ok, g, mk1);
-        relu_mask<4>(da, mk1);
+        relu_mask<4>(da, mk1);   // (twin: neck_bwd_kernel)
         st_rm<4>(a.dpre0 + row * 64, ok, g, da);
         if (a.dx) {
             Opd<2> dao;
-            make_opd<4>(da, dao);
             f32x4 de[KT0];
-            zero<KT0>(de);
-            tgemm<2, KT0>(w0p, dao, de);
+            input_grad<KT0>(w0p, da, dao, de);
             if constexpr (F == 0) st_rm_k<KT0>(a.dx + row * a.lddx, ok, g, a.k0, de);
             else st_lm<KT0, F>(a.dx, a.n, a.n_levels, row, ok, g, de);
         }
@@ -2329,16 +2367,68 @@ __global__ __launch_bounds__((rmlp_w_threads<NL, NTO>()), (rmlp_w_threads<NL, NT
     for (int i = threadIdx.x; i < 64; i += (int)blockDim.x) p1[64 * a.k0 + i] = rb0[i];
 }
 
-static inline uint32_t fused_grid(int64_t work_items, int threads = kFThreads) {
-    const int waves = threads / 64;
-    int64_t blocks = (work_items + waves - 1) / waves;
-    if (blocks > 512) blocks = 512;  // persistent: 2 workgroups per CU
+// ---- host side: grid, launch, the compile-time rungs, the rgb head's weight views ---------------------------------------------------------
+// Persistent launches: one wave per work item up to `cap` workgroups (512: two workgroups per CU; 256: one per CU), at least one
+static inline uint32_t persistent_grid(int64_t items, int waves_per_wg, int64_t cap) {
+    int64_t blocks = (items + waves_per_wg - 1) / waves_per_wg;
+    if (blocks > cap) blocks = cap;
     return (uint32_t)(blocks < 1 ? 1 : blocks);
 }
+// the four-waves-per-SIMD kernels: 512-lane workgroups, two per CU.  Row kernels take chunks of kNeckChunk tiles, per-ray kernels rays.
+static inline uint32_t row_chunk_grid(int64_t n) { return persistent_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads / 64, 512); }
+static inline uint32_t ray_grid(int64_t n_rays) { return persistent_grid(n_rays, kNThreads / 64, 512); }
 
-template <typename K>
-static int set_lds(K kern, size_t lds, const char *what) {
-    return reserve_lds(reinterpret_cast<const void *>(kern), lds, what);
+template <class K, class A, class... More>
+static int launch(K kern, uint32_t grid, int threads, size_t lds, hipStream_t st, const char *what, const A &a, More... more) {
+    if (lds)
+        if (int r = reserve_lds(reinterpret_cast<const void *>(kern), lds, what)) return r;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a, more...);
+    return check_launch(what);
+}
+
+// The compile-time rungs.  pick4: fn(I<V>) for a run-time v in 1..4 (below MIN: the MIN rung).  dispatch_kt0_f: fn(I<KT0>, I<F>) with
+// KT0 = input tiles of the first layer for k0 features, F = n_feat among FS...; a row-major input (F = 0) always runs four tiles (its loads
+// mask the columns), and a kernel family without a KT0 = 1 instantiation (the plain heads) passes MIN = 2.  The kernels' LDS layouts are
+// templates of the same constants, so the mapping from (k0, n_feat) to an instantiation is written here only.
+template <int V> using I = std::integral_constant<int, V>;
+#define RUNG(c) (std::remove_reference_t<decltype(c)>::value)   // the constant a rung handed to a generic lambda
+template <int MIN, class Fn>
+static int pick4(int v, Fn &&fn) {
+    if constexpr (MIN <= 1) {
+        if (v <= 1) return fn(I<1>{});
+    }
+    if (v <= 2) return fn(I<2>{});
+    if (v == 3) return fn(I<3>{});
+    return fn(I<4>{});
+}
+template <int MIN, int F, class Fn>
+static int pick_kt0(int k0, Fn &fn) {
+    if constexpr (F == 0) return fn(I<4>{}, I<0>{});
+    else return pick4<MIN>((k0 + 15) / 16, [&](auto kt0) { return fn(kt0, I<F>{}); });
+}
+template <int MIN, int... FS, class Fn>
+static int dispatch_kt0_f(int k0, int n_feat, Fn fn) {
+    int rc = EMER_E_INVALID;
+    (void)((n_feat == FS ? (rc = pick_kt0<MIN, FS>(k0, fn), true) : false) || ...);
+    return rc;
+}
+// ... and (NL, NTO) of the plain heads: 2 or 3 layers, an output of one or four 16-column tiles
+static inline int rmlp_nto(int n_out) { return n_out <= 16 ? 1 : 4; }
+template <class Fn>
+static int dispatch_nl_nto(int n_layers, int n_out, Fn fn) {
+    if (n_layers == 2) return rmlp_nto(n_out) == 1 ? fn(I<2>{}, I<1>{}) : fn(I<2>{}, I<4>{});
+    return rmlp_nto(n_out) == 1 ? fn(I<3>{}, I<1>{}) : fn(I<3>{}, I<4>{});
+}
+
+// Views of a torch Linear weight block w [n][ld >= k] for stage_w3: as it is, or transposed ((n, k) = w[k][n]: the backward's operand)
+static inline WSrc w_view(const float *w, int64_t ld, int n, int k) { return WSrc{w, ld, 1, n, k}; }
+static inline WSrc w_view_t(const float *w, int64_t ld, int n, int k) { return WSrc{w, 1, ld, k, n}; }
+// The rgb head's per-sample blocks of w0 [64][kh + 64] = [W0h | W0g], w1 [64][64 + kh + 64] = [W1a | W1h | W1g], w2 [3][64]
+struct RgbViews { WSrc w0g, w1a, w1g, w2; };
+static inline RgbViews rgb_views(const float *w0, const float *w1, const float *w2, int32_t kh, bool transposed) {
+    const int64_t k0 = kh + 64, k1 = 64 + k0;
+    const auto v = transposed ? w_view_t : w_view;
+    return RgbViews{v(w0 + kh, k0, 64, 64), v(w1, k1, 64, 64), v(w1 + 64 + kh, k1, 64, 64), v(w2, 64, 3, 64)};
 }
 
 }  // namespace emer
@@ -2351,22 +2441,6 @@ extern "C" int emer_neck_supported(int32_t n_levels, int32_t n_feat, int32_t hid
     const bool f_ok = n_feat == 1 || n_feat == 2 || n_feat == 4 || n_feat == 8;
     return (f_ok && k0 >= 1 && k0 <= 64 && hidden == 64 && (n_out == 1 || n_out == 64 || n_out == 128)) ? 1 : 0;
 }
-
-#define EMER_NECK_DISPATCH(KERNEL, NTX, ARGS, LDS, WHAT)                                                        \
-    do {                                                                                                       \
-        const int kt0 = (k0 + 15) / 16;                                                                        \
-        int rc_ = EMER_E_INVALID;                                                                                  \
-        auto go = [&](auto kern) {                                                                             \
-            if (int r = set_lds(kern, LDS(kt0), WHAT)) return r;                                               \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kNThreads), LDS(kt0), st, ARGS);                         \
-            return check_launch(WHAT);                                                                         \
-        };                                                                                                     \
-        if (n_feat == 1) { if (kt0 == 1) rc_ = go(KERNEL<1, 1, NTX>); else if (kt0 == 2) rc_ = go(KERNEL<2, 1, NTX>); else if (kt0 == 3) rc_ = go(KERNEL<3, 1, NTX>); else rc_ = go(KERNEL<4, 1, NTX>); } \
-        else if (n_feat == 2) { if (kt0 == 1) rc_ = go(KERNEL<1, 2, NTX>); else if (kt0 == 2) rc_ = go(KERNEL<2, 2, NTX>); else if (kt0 == 3) rc_ = go(KERNEL<3, 2, NTX>); else rc_ = go(KERNEL<4, 2, NTX>); } \
-        else if (n_feat == 4) { if (kt0 == 1) rc_ = go(KERNEL<1, 4, NTX>); else if (kt0 == 2) rc_ = go(KERNEL<2, 4, NTX>); else if (kt0 == 3) rc_ = go(KERNEL<3, 4, NTX>); else rc_ = go(KERNEL<4, 4, NTX>); } \
-        else { if (kt0 == 1) rc_ = go(KERNEL<1, 8, NTX>); else if (kt0 == 2) rc_ = go(KERNEL<2, 8, NTX>); else if (kt0 == 3) rc_ = go(KERNEL<3, 8, NTX>); else rc_ = go(KERNEL<4, 8, NTX>); } \
-        return rc_;                                                                                            \
-    } while (0)
 
 // enc_lm [L][n][F] -> h1 = relu(enc W0^T + b0) [n][64] -> out = h1 W1^T + b1.
 // n_out == 64 / 128: out0 [n][64] (features 0..63), out1 [n][64] (features 64..127), dens = exp(out[:,0] - 1) if non-null;
@@ -2386,23 +2460,15 @@ extern "C" int emer_neck_fwd(const float *enc_lm, int32_t n_levels, int32_t n_fe
     a.w1 = WSrc{w1, 64, 1, n_out, 64};
     a.b0 = b0; a.b1 = b1; a.h1 = h1; a.out0 = out0; a.out1 = out1; a.dens = dens;
     hipStream_t st = as_stream(stream);
-    const uint32_t grid = fused_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads);
-    if (n_out == 1 && k0 <= 16) {  // narrow input (the proposal networks): fp32 matrix instruction, weights in registers
-        const int ks4 = (k0 + 3) / 4;
-#define EMER_DENS(KS) hipLaunchKernelGGL(density_fwd_kernel<KS>, dim3(grid), dim3(kNThreads), 0, st, a, n_feat)
-        if (ks4 == 1) EMER_DENS(1); else if (ks4 == 2) EMER_DENS(2); else if (ks4 == 3) EMER_DENS(3); else EMER_DENS(4);
-#undef EMER_DENS
-        return check_launch("neck_fwd");
-    } else if (n_out == 1) {
-        auto lds = [](int kt0) { return (size_t)(w3_units(4, (kt0 + 1) / 2) + w3_units(1, 2)) * 16 + (64 + 16 + 64) * sizeof(float); };
-        EMER_NECK_DISPATCH(neck_fwd_kernel, 1, a, lds, "neck_fwd");
-    } else if (n_out == 64) {
-        auto lds = [](int kt0) { return (size_t)(w3_units(4, (kt0 + 1) / 2) + w3_units(4, 2)) * 16 + (64 + 64 + 64) * sizeof(float); };
-        EMER_NECK_DISPATCH(neck_fwd_kernel, 4, a, lds, "neck_fwd");
-    } else {
-        auto lds = [](int kt0) { return (size_t)(w3_units(4, (kt0 + 1) / 2) + w3_units(8, 2)) * 16 + (64 + 128 + 64) * sizeof(float); };
-        EMER_NECK_DISPATCH(neck_fwd_kernel, 8, a, lds, "neck_fwd");
-    }
+    const uint32_t grid = row_chunk_grid(n);
+    if (n_out == 1 && k0 <= 16)  // narrow input (the proposal networks): fp32 matrix instruction, weights in registers
+        return pick4<1>((k0 + 3) / 4, [&](auto ks4) { return launch(density_fwd_kernel<RUNG(ks4)>, grid, kNThreads, 0, st, "neck_fwd", a, n_feat); });
+    return dispatch_kt0_f<1, 1, 2, 4, 8>(k0, n_feat, [&](auto kt0, auto f) {
+        auto go = [&](auto nt1) {
+            return launch(neck_fwd_kernel<RUNG(kt0), RUNG(f), RUNG(nt1)>, grid, kNThreads, NeckFwdLds<RUNG(kt0), RUNG(nt1)>::bytes, st, "neck_fwd", a);
+        };
+        return n_out == 1 ? go(I<1>{}) : n_out == 64 ? go(I<4>{}) : go(I<8>{});
+    });
 }
 
 // Data-gradient chain of emer_neck_fwd.  d0 / d1: gradients of output features 0..63 / 64..127 (either may be NULL
@@ -2423,31 +2489,21 @@ extern "C" int emer_neck_bwd(const float *d0, const float *d1, const float *dden
     a.dpre1 = dpre1; a.dcol0 = dcol0; a.dpre0 = dpre0; a.denc = denc_lm;
     a.w0t = WSrc{w0, 1, k0, k0, 64};     // (n = input feature, k = hidden) = w0[k][n]
     hipStream_t st = as_stream(stream);
-    const uint32_t grid = fused_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads);
-    if (n_out == 1) {
-        a.w1t = WSrc{w1, 1, 64, 64, 1};  // (n = hidden, k = 0) = w1[0][n]
-        auto lds = [](int kt0) { return (size_t)w3_units(kt0, 2) * 16 + 64 * sizeof(float); };
-        EMER_NECK_DISPATCH(neck_bwd_kernel, 0, a, lds, "neck_bwd");
-    } else if (n_out == 64 || !d1) {
-        a.w1t = WSrc{w1, 1, 64, 64, 64};  // only the first 64 outputs carry a gradient
-        auto lds = [](int kt0) { return (size_t)(w3_units(kt0, 2) + w3_units(4, 2)) * 16; };
-        EMER_NECK_DISPATCH(neck_bwd_kernel, 4, a, lds, "neck_bwd");
-    } else {
-        a.w1t = WSrc{w1, 1, 64, 64, 128};
-        auto lds = [](int kt0) { return (size_t)(w3_units(kt0, 2) + w3_units(4, 4)) * 16; };
-        EMER_NECK_DISPATCH(neck_bwd_kernel, 8, a, lds, "neck_bwd");
-    }
+    const uint32_t grid = row_chunk_grid(n);
+    // W1^T: density mode (n = hidden, k = 0) = w1[0][n]; 64 columns when only the first 64 outputs carry a gradient; else 128
+    const int kt1 = n_out == 1 ? 0 : (n_out == 64 || !d1) ? 4 : 8;
+    a.w1t = w_view_t(w1, 64, kt1 == 0 ? 1 : 16 * kt1, 64);
+    return dispatch_kt0_f<1, 1, 2, 4, 8>(k0, n_feat, [&](auto kt0, auto f) {
+        auto go = [&](auto k1) {
+            return launch(neck_bwd_kernel<RUNG(kt0), RUNG(f), RUNG(k1)>, grid, kNThreads, NeckBwdLds<RUNG(kt0), RUNG(k1)>::bytes, st, "neck_bwd", a);
+        };
+        return kt1 == 0 ? go(I<0>{}) : kt1 == 4 ? go(I<4>{}) : go(I<8>{});
+    });
 }
 
 // ---- neck backward with the weight gradients fused [r3] --------------------------------------------------------------------
-static inline uint32_t neck_bwdw_grid(int64_t n, int kt0, int no) {
-    const int64_t tiles = (n + 15) / 16;
-    const int nw = neckw_threads(kt0, no) / 64;
-    int64_t blocks = (tiles + nw - 1) / nw;
-    if (blocks > 256) blocks = 256;   // persistent: one workgroup per CU
-    return (uint32_t)(blocks < 1 ? 1 : blocks);
-}
-static inline size_t neck_bwdw_lds(int kt0, int no) {   // weights + bias + a staging buffer of 4-8 KB per wave; the final reduction reuses the front
+static inline uint32_t neck_bwdw_grid(int64_t n, int no) { return persistent_grid((n + 15) / 16, neckw_threads(0, no) / 64, 256); }   // one workgroup per CU
+static constexpr size_t neck_bwdw_lds(int kt0, int no) {   // weights + bias + a staging buffer of 4-8 KB per wave; the final reduction reuses the front
     const size_t w = (size_t)(w3_units(kt0, 2) + w3_units(4, 2 * no) + w3_units(4, (kt0 + 1) / 2)) * 16
                      + (size_t)(64 + (neckw_threads(kt0, no) / 64) * (1024 * no + 384 * kt0)) * sizeof(float);
     const size_t r = (size_t)(64 * no * 65 + 64 * 16 * kt0 + 64) * sizeof(float);
@@ -2464,7 +2520,7 @@ static inline bool neck_bwdw_fits(int32_t n_levels, int32_t n_feat, int64_t n) {
 // floats of workspace emer_neck_bwd_fused needs (per-workgroup partial weight gradients)
 extern "C" int64_t emer_neck_bwd_fused_workspace(int32_t n_levels, int32_t n_feat, int64_t n, int32_t n_out) {
     if (n <= 0 || !emer_neck_bwd_fused_supported(n_levels, n_feat, 64, n_out) || !neck_bwdw_fits(n_levels, n_feat, n)) return 0;
-    return (int64_t)neck_bwdw_grid(n, (n_levels * n_feat + 15) / 16, n_out / 64) * neck_bwdw_stride(n_levels * n_feat, n_out);
+    return (int64_t)neck_bwdw_grid(n, n_out / 64) * neck_bwdw_stride(n_levels * n_feat, n_out);
 }
 // Backward of emer_neck_fwd (n_out == 64 or 128) INCLUDING the weight gradients: writes denc_lm [L][n][F]; ACCUMULATES (+=) dw0
 // [64][ld_dw0 >= L*F], db0 [64], dw1 [n_out][ld_dw1 >= 64], db1 [n_out] (torch Linear layouts; what autograd's AccumulateGrad would
@@ -2491,19 +2547,15 @@ extern "C" int emer_neck_bwd_fused(const float *d0, const float *d1, const float
     a.w1t = WSrc{w1, 1, 64, 64, n_out};       // (n = hidden, k = output) = w1[k][n]
     a.denc = denc_lm; a.partials = workspace; a.stride = neck_bwdw_stride(k0, n_out);
     hipStream_t st = as_stream(stream);
-    const int kt0 = (k0 + 15) / 16, no = n_out / 64;
-    const uint32_t grid = neck_bwdw_grid(n, kt0, no);
-    const size_t lds = neck_bwdw_lds(kt0, no);
-    int rc = EMER_E_INVALID;
-    auto go = [&](auto kern) {
-        if (int r = set_lds(kern, lds, "neck_bwd_fused")) return r;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(neckw_threads(kt0, no)), lds, st, a);
-        return check_launch("neck_bwd_fused");
-    };
-#define EMER_NBW(FF, NN) (kt0 == 1 ? go(neck_bwdw_kernel<1, FF, NN>) : kt0 == 2 ? go(neck_bwdw_kernel<2, FF, NN>) : kt0 == 3 ? go(neck_bwdw_kernel<3, FF, NN>) : go(neck_bwdw_kernel<4, FF, NN>))
-    if (no == 1) { if (n_feat == 1) rc = EMER_NBW(1, 1); else if (n_feat == 2) rc = EMER_NBW(2, 1); else if (n_feat == 4) rc = EMER_NBW(4, 1); else rc = EMER_NBW(8, 1); }
-    else { if (n_feat == 1) rc = EMER_NBW(1, 2); else if (n_feat == 2) rc = EMER_NBW(2, 2); else if (n_feat == 4) rc = EMER_NBW(4, 2); else rc = EMER_NBW(8, 2); }
-#undef EMER_NBW
+    const int no = n_out / 64;
+    const uint32_t grid = neck_bwdw_grid(n, no);
+    const int rc = dispatch_kt0_f<1, 1, 2, 4, 8>(k0, n_feat, [&](auto kt0, auto f) {
+        auto go = [&](auto nn) {
+            return launch(neck_bwdw_kernel<RUNG(kt0), RUNG(f), RUNG(nn)>, grid, neckw_threads(RUNG(kt0), RUNG(nn)), neck_bwdw_lds(RUNG(kt0), RUNG(nn)), st,
+                          "neck_bwd_fused", a);
+        };
+        return no == 1 ? go(I<1>{}) : go(I<2>{});
+    });
     if (rc) return rc;
     const DwReduceJob jb[2] = {{0, n_out, 64, dw1, ld_dw1, db1, 0, {0}, {0}, {0}}, {(int64_t)n_out * 65, 64, k0, dw0, ld_dw0, db0, 0, {0}, {0}, {0}}};
     return launch_dw_reduce_multi(workspace, (int32_t)grid, a.stride, 2, jb, st);
@@ -2516,7 +2568,7 @@ static inline int64_t dens_bwdw_stride(int k0) { return ((int64_t)64 * k0 + 129 
 extern "C" int64_t emer_density_bwd_fused_workspace(int32_t n_levels, int32_t n_feat, int64_t n) {
     const int k0 = n_levels * n_feat;
     if (n <= 0 || k0 < 1 || k0 > 16 || !emer_neck_supported(n_levels, n_feat, 64, 1)) return 0;
-    return (int64_t)fused_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads) * dens_bwdw_stride(k0);
+    return (int64_t)row_chunk_grid(n) * dens_bwdw_stride(k0);
 }
 extern "C" int emer_density_bwd_fused(const float *ddens, const float *dens, const float *enc_lm, int32_t n_levels, int32_t n_feat, int64_t n,
                                       const float *w0, const float *b0, const float *w1, float *denc_lm, float *workspace, float *dw0,
@@ -2531,12 +2583,9 @@ extern "C" int emer_density_bwd_fused(const float *ddens, const float *dens, con
     a.w0 = WSrc{w0, k0, 1, 64, k0};
     a.b0 = b0; a.w1 = w1; a.denc = denc_lm; a.partials = workspace; a.stride = dens_bwdw_stride(k0);
     hipStream_t st = as_stream(stream);
-    const uint32_t grid = fused_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads);
-    const int ks4 = (k0 + 3) / 4;
-#define EMER_DBW(KS) hipLaunchKernelGGL(density_bwdw_kernel<KS>, dim3(grid), dim3(kNThreads), 0, st, a, n_feat)
-    if (ks4 == 1) EMER_DBW(1); else if (ks4 == 2) EMER_DBW(2); else if (ks4 == 3) EMER_DBW(3); else EMER_DBW(4);
-#undef EMER_DBW
-    if (int rc = check_launch("density_bwd_fused")) return rc;
+    const uint32_t grid = row_chunk_grid(n);
+    if (int rc = pick4<1>((k0 + 3) / 4, [&](auto ks4) { return launch(density_bwdw_kernel<RUNG(ks4)>, grid, kNThreads, 0, st, "density_bwd_fused", a, n_feat); }))
+        return rc;
     const DwReduceJob jb[2] = {{0, 64, k0, dw0, ld_dw0, db0, 0, {0}, {0}, {0}}, {64 * k0 + 64, 1, 64, dw1, 64, db1, 0, {0}, {0}, {0}}};
     return launch_dw_reduce_multi(workspace, (int32_t)grid, a.stride, 2, jb, st);
 }
@@ -2554,16 +2603,10 @@ extern "C" int emer_rgb_head_fwd(const float *geo, int64_t ld_geo, const float *
                  "rgb_head_fwd: bad arguments");
     RgbFwdArgs a;
     a.geo = geo; a.ld_geo = ld_geo; a.rb0 = rb0; a.rb1 = rb1; a.ld_rb = ld_rb; a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
-    const int64_t k0 = kh + 64, k1 = 64 + k0;
-    a.w0g = WSrc{w0 + kh, k0, 1, 64, 64};
-    a.w1a = WSrc{w1, k1, 1, 64, 64};
-    a.w1g = WSrc{w1 + 64 + kh, k1, 1, 64, 64};
-    a.w2 = WSrc{w2, 64, 1, 3, 64};
+    const RgbViews v = rgb_views(w0, w1, w2, kh, false);
+    a.w0g = v.w0g; a.w1a = v.w1a; a.w1g = v.w1g; a.w2 = v.w2;
     a.b2 = b2; a.a1 = a1; a.a2 = a2; a.out = out;
-    const size_t lds = (size_t)(3 * w3_units(4, 2) + w3_units(1, 2)) * 16 + 16 * sizeof(float);
-    if (int rc = set_lds(rgb_fwd_kernel, lds, "rgb_head_fwd")) return rc;
-    hipLaunchKernelGGL(rgb_fwd_kernel, dim3(fused_grid(n_rays, kNThreads)), dim3(kNThreads), lds, as_stream(stream), a);
-    return check_launch("rgb_head_fwd");
+    return launch(rgb_fwd_kernel, ray_grid(n_rays), kNThreads, RgbFwdLds::bytes, as_stream(stream), "rgb_head_fwd", a);
 }
 
 // 1 when emer_field_fwd covers a neck of this input shape (64 hidden, 64 geometry features) followed by the rgb head
@@ -2592,26 +2635,14 @@ extern "C" int emer_field_fwd(const float *enc_lm, int32_t n_levels, int32_t n_f
     a.nw1 = WSrc{nw1, 64, 1, 64, 64};
     a.nb0 = nb0; a.nb1 = nb1; a.geo = geo; a.dens = dens;
     a.r.geo = nullptr; a.r.ld_geo = 64; a.r.rb0 = rb0; a.r.rb1 = rb1; a.r.ld_rb = ld_rb; a.r.tiles_per_ray = samples_per_ray / 16; a.r.n_rays = n_rays;
-    const int64_t kk0 = kh + 64, kk1 = 64 + kk0;
-    a.r.w0g = WSrc{w0 + kh, kk0, 1, 64, 64};
-    a.r.w1a = WSrc{w1, kk1, 1, 64, 64};
-    a.r.w1g = WSrc{w1 + 64 + kh, kk1, 1, 64, 64};
-    a.r.w2 = WSrc{w2, 64, 1, 3, 64};
+    const RgbViews v = rgb_views(w0, w1, w2, kh, false);
+    a.r.w0g = v.w0g; a.r.w1a = v.w1a; a.r.w1g = v.w1g; a.r.w2 = v.w2;
     a.r.b2 = b2; a.r.a1 = a1; a.r.a2 = a2; a.r.out = out;
-    const int kt0 = (k0 + 15) / 16;
-    const size_t lds = (size_t)(w3_units(4, (kt0 + 1) / 2) + 4 * w3_units(4, 2) + w3_units(1, 2)) * 16 + (64 + 64 + 16) * sizeof(float);
     hipStream_t st = as_stream(stream);
-    int64_t blocks = (n_rays + kFieldThreads / 64 - 1) / (kFieldThreads / 64);
-    const uint32_t grid = (uint32_t)(blocks > 256 ? 256 : blocks);  // persistent: one workgroup per CU
-    int rc = EMER_E_INVALID;
-    auto go = [&](auto kern) {
-        if (int r = set_lds(kern, lds, "field_fwd")) return r;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kFieldThreads), lds, st, a);
-        return check_launch("field_fwd");
-    };
-    if (n_feat == 2) { if (kt0 == 1) rc = go(field_fwd_kernel<1, 2>); else if (kt0 == 2) rc = go(field_fwd_kernel<2, 2>); else if (kt0 == 3) rc = go(field_fwd_kernel<3, 2>); else rc = go(field_fwd_kernel<4, 2>); }
-    else { if (kt0 == 1) rc = go(field_fwd_kernel<1, 4>); else if (kt0 == 2) rc = go(field_fwd_kernel<2, 4>); else if (kt0 == 3) rc = go(field_fwd_kernel<3, 4>); else rc = go(field_fwd_kernel<4, 4>); }
-    return rc;
+    const uint32_t grid = persistent_grid(n_rays, kFieldThreads / 64, 256);  // one workgroup per CU
+    return dispatch_kt0_f<1, 2, 4>(k0, n_feat, [&](auto kt0, auto f) {
+        return launch(field_fwd_kernel<RUNG(kt0), RUNG(f)>, grid, kFieldThreads, FieldFwdLds<RUNG(kt0)>::bytes, st, "field_fwd", a);
+    });
 }
 
 // rgb head data-gradient chain.  Writes dpre2 [n][3], dpre1 / dpre0 / dgeo [n][64] and the per-ray sums s1 / s0
@@ -2626,28 +2657,18 @@ extern "C" int emer_rgb_head_bwd(const float *dout, const float *out, const floa
     EMER_REQUIRE(!dw2 || (workspace && ld_dw2 >= 64), "rgb_head_bwd: dw2 needs emer_rgb_head_bwd_workspace floats of workspace and ld_dw2 >= 64");
     RgbBwdArgs a;
     a.dout = dout; a.out = out; a.a1 = a1; a.a2 = a2; a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
-    const int64_t k0 = kh + 64, k1 = 64 + k0;
-    a.w2t = WSrc{w2, 1, 64, 64, 3};               // (n = hidden, k = channel) = w2[k][n]
-    a.w1at = WSrc{w1, 1, k1, 64, 64};             // (n = a1 feature, k = layer-1 output) = w1[k][n]
-    a.w1gt = WSrc{w1 + 64 + kh, 1, k1, 64, 64};
-    a.w0gt = WSrc{w0 + kh, 1, k0, 64, 64};
+    const RgbViews v = rgb_views(w0, w1, w2, kh, true);   // W2^T (n = hidden, k = channel) = w2[k][n], W1a^T (n = a1 feature, k = layer-1 output), ...
+    a.w2t = v.w2; a.w1at = v.w1a; a.w1gt = v.w1g; a.w0gt = v.w0g;
     a.dpre2 = dpre2; a.dpre1 = dpre1; a.dpre0 = dpre0; a.dgeo = dgeo; a.s1 = s1; a.s0 = s0;
     a.w2part = dw2 ? workspace : nullptr;
-    const size_t lds = (size_t)(3 * w3_units(4, 2)) * 16;
-    if (int rc = set_lds(rgb_bwd_kernel, lds, "rgb_head_bwd")) return rc;
-    const uint32_t grid = fused_grid(n_rays, kNThreads);
-    hipLaunchKernelGGL(rgb_bwd_kernel, dim3(grid), dim3(kNThreads), lds, as_stream(stream), a);
-    if (int rc = check_launch("rgb_head_bwd")) return rc;
+    const uint32_t grid = ray_grid(n_rays);
+    if (int rc = launch(rgb_bwd_kernel, grid, kNThreads, RgbBwdLds::bytes, as_stream(stream), "rgb_head_bwd", a)) return rc;
     if (dw2) return launch_dw_reduce(workspace, (int32_t)grid, 196, 3, 64, dw2, ld_dw2, db2, as_stream(stream));
     return EMER_OK;
 }
 
 // ---- rgb head backward with the weight gradients of layers 0 / 1 (per-sample column blocks) and 2 fused [r4] -------------------------
-static inline uint32_t rgb_bwdw_grid(int64_t n_rays) {
-    int64_t blocks = (n_rays + kRWThreads / 64 - 1) / (kRWThreads / 64);
-    if (blocks > 256) blocks = 256;   // persistent: one 4-wave workgroup per CU (one wave per SIMD)
-    return (uint32_t)(blocks < 1 ? 1 : blocks);
-}
+static inline uint32_t rgb_bwdw_grid(int64_t n_rays) { return persistent_grid(n_rays, kRWThreads / 64, 256); }   // one 4-wave workgroup per CU (one wave per SIMD)
 static constexpr int64_t kRgbBwdWStride = 64 * 128 + 64 * 64 + 196;
 // 1 when emer_rgb_head_bwd_fused covers the shape (whole 16-row tiles per ray, as emer_rgb_head_bwd)
 extern "C" int emer_rgb_head_bwd_fused_supported(int32_t samples_per_ray) {
@@ -2673,11 +2694,8 @@ static int rgb_bwdw_run(const char *who, RgbBwdWArgs &a, bool own_ptrs, bool own
     EMER_REQUIRE(own_ld && ld_geo >= 64 && ld_geo % 4 == 0 && ld_dw0 >= 64 + kh && ld_dw1 >= 128 + kh && ld_dw2 >= 64, "%s: bad leading dimension", who);
     EMER_REQUIRE(n_rays * samples_per_ray * ld_geo < ((int64_t)1 << 40), "%s: batch too large", who);
     a.dout = dout; a.out = out; a.a1 = nullptr; a.a2 = nullptr; a.geo = geo; a.ld_geo = ld_geo; a.tiles_per_ray = samples_per_ray / 16; a.n_rays = n_rays;
-    const int64_t k0 = kh + 64, k1 = 64 + k0;
-    a.w2t = WSrc{w2, 1, 64, 64, 3};
-    a.w1at = WSrc{w1, 1, k1, 64, 64};
-    a.w1gt = WSrc{w1 + 64 + kh, 1, k1, 64, 64};
-    a.w0gt = WSrc{w0 + kh, 1, k0, 64, 64};
+    const RgbViews vt = rgb_views(w0, w1, w2, kh, true);
+    a.w2t = vt.w2; a.w1at = vt.w1a; a.w1gt = vt.w1g; a.w0gt = vt.w0g;
     a.dgeo = dgeo; a.s1 = s1; a.s0 = s0; a.partials = workspace; a.stride = kRgbBwdWStride;
     hipStream_t st = as_stream(stream);
     const uint32_t grid = rgb_bwdw_grid(n_rays);
@@ -2706,7 +2724,7 @@ extern "C" int emer_rgb_head_bwd_fused(const float *dout, const float *out, cons
                         workspace, dw0, ld_dw0, dw1, ld_dw1, dw2, ld_dw2, db2, stream, [&](uint32_t grid, hipStream_t st) -> int {
         a.a1 = a1; a.a2 = a2;
         const size_t lds = (size_t)(3 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * (2048 + 3072) * sizeof(float);
-        if (int rc = set_lds(rgb_bwdw16_kernel, lds, "rgb_head_bwd_fused")) return rc;
+        if (int rc = reserve_lds(reinterpret_cast<const void *>(rgb_bwdw16_kernel), lds, "rgb_head_bwd_fused")) return rc;
         hipLaunchKernelGGL(rgb_bwdw16_kernel, dim3(grid), dim3(kRWThreads), lds, st, a);
         return EMER_OK;
     });
@@ -2724,16 +2742,14 @@ extern "C" int emer_rgb_head_bwd_recompute(const float *dout, const float *out, 
     return rgb_bwdw_run("rgb_head_bwd_recompute", a, rb0 && rb1, ld_rb >= 64, dout, out, geo, ld_geo, n_rays, samples_per_ray, kh, w0, w1, w2, dgeo,
                         s1, s0, workspace, dw0, ld_dw0, dw1, ld_dw1, dw2, ld_dw2, db2, stream, [&](uint32_t grid, hipStream_t st) -> int {
         a.a1 = a1; a.rb0 = rb0; a.rb1 = rb1; a.ld_rb = ld_rb;
-        const int64_t k0 = kh + 64, k1 = 64 + k0;
-        a.w0g = WSrc{w0 + kh, k0, 1, 64, 64};
-        a.w1a = WSrc{w1, k1, 1, 64, 64};
-        a.w1g = WSrc{w1 + 64 + kh, k1, 1, 64, 64};
+        const RgbViews v = rgb_views(w0, w1, w2, kh, false);
+        a.w0g = v.w0g; a.w1a = v.w1a; a.w1g = v.w1g;
         const size_t lds = (size_t)(6 * w3_units(4, 2)) * 16 + (size_t)(kRWThreads / 64) * 256 * sizeof(float);
         if (a1) {   // the cheaper half: a1 stored by the forward, a2 recomputed
-            if (int rc = set_lds(rgb_bwdwr_kernel<true>, lds, "rgb_head_bwd_recompute")) return rc;
+            if (int rc = reserve_lds(reinterpret_cast<const void *>(rgb_bwdwr_kernel<true>), lds, "rgb_head_bwd_recompute")) return rc;
             hipLaunchKernelGGL(rgb_bwdwr_kernel<true>, dim3(grid), dim3(kRWThreads), lds, st, a);
         } else {
-            if (int rc = set_lds(rgb_bwdwr_kernel<false>, lds, "rgb_head_bwd_recompute")) return rc;
+            if (int rc = reserve_lds(reinterpret_cast<const void *>(rgb_bwdwr_kernel<false>), lds, "rgb_head_bwd_recompute")) return rc;
             hipLaunchKernelGGL(rgb_bwdwr_kernel<false>, dim3(grid), dim3(kRWThreads), lds, st, a);
         }
         return EMER_OK;
@@ -2742,7 +2758,7 @@ extern "C" int emer_rgb_head_bwd_recompute(const float *dout, const float *out, 
 
 // floats of workspace emer_rgb_head_bwd needs when it also produces dw2 / db2
 extern "C" int64_t emer_rgb_head_bwd_workspace(int64_t n_rays) {
-    return n_rays <= 0 ? 0 : (int64_t)fused_grid(n_rays, kNThreads) * 196;
+    return n_rays <= 0 ? 0 : (int64_t)ray_grid(n_rays) * 196;
 }
 
 // ---- plain 2- / 3-layer heads -------------------------------------------------------------------------------------
@@ -2752,30 +2768,6 @@ extern "C" int emer_rmlp_supported(int32_t n_layers, int32_t k0, int32_t n_feat,
     const bool in_ok = (n_feat == 0 && k0 % 4 == 0) || (n_feat == 4 && k0 % 4 == 0);
     return ((n_layers == 2 || n_layers == 3) && in_ok && k0 >= 4 && k0 <= 64 && hidden == 64 && n_out >= 1 && n_out <= 64) ? 1 : 0;
 }
-
-#define EMER_RMLP_DISPATCH(KERNEL, ARGS, LDS, WHAT)                                                                      \
-    do {                                                                                                               \
-        int rc_ = EMER_E_INVALID;                                                                                      \
-        auto go = [&](auto kern) {                                                                                     \
-            if (int r = set_lds(kern, LDS, WHAT)) return r;                                                            \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kNThreads), LDS, st, ARGS);                                      \
-            return check_launch(WHAT);                                                                                 \
-        };                                                                                                             \
-        if (n_feat == 0) {                                                                                             \
-            if (n_layers == 2) { if (nto == 1) rc_ = go(KERNEL<4, 0, 2, 1>); else rc_ = go(KERNEL<4, 0, 2, 4>); }      \
-            else               { if (nto == 1) rc_ = go(KERNEL<4, 0, 3, 1>); else rc_ = go(KERNEL<4, 0, 3, 4>); }      \
-        } else if (kt0 <= 2) {                                                                                         \
-            if (n_layers == 2) { if (nto == 1) rc_ = go(KERNEL<2, 4, 2, 1>); else rc_ = go(KERNEL<2, 4, 2, 4>); }      \
-            else               { if (nto == 1) rc_ = go(KERNEL<2, 4, 3, 1>); else rc_ = go(KERNEL<2, 4, 3, 4>); }      \
-        } else if (kt0 == 3) {                                                                                         \
-            if (n_layers == 2) { if (nto == 1) rc_ = go(KERNEL<3, 4, 2, 1>); else rc_ = go(KERNEL<3, 4, 2, 4>); }      \
-            else               { if (nto == 1) rc_ = go(KERNEL<3, 4, 3, 1>); else rc_ = go(KERNEL<3, 4, 3, 4>); }      \
-        } else {                                                                                                       \
-            if (n_layers == 2) { if (nto == 1) rc_ = go(KERNEL<4, 4, 2, 1>); else rc_ = go(KERNEL<4, 4, 2, 4>); }      \
-            else               { if (nto == 1) rc_ = go(KERNEL<4, 4, 3, 1>); else rc_ = go(KERNEL<4, 4, 3, 4>); }      \
-        }                                                                                                              \
-        return rc_;                                                                                                    \
-    } while (0)
 
 // x: row-major [n][ldx] (n_feat == 0, n_levels ignored) or level-major [n_levels][n][n_feat] with k0 = n_levels * n_feat.
 // Weights in torch Linear layout: w0 [64][k0], (w1 [64][64],) w_last [n_out][64]; for two layers pass w2 = b2 = NULL and
@@ -2796,12 +2788,14 @@ extern "C" int emer_rmlp_fwd(const float *x, int64_t ldx, int32_t n_levels, int3
     a.w1 = WSrc{w1, 64, 1, n_layers == 2 ? n_out : 64, 64};
     a.w2 = WSrc{w2, 64, 1, n_out, 64};
     a.b0 = b0; a.b1 = b1; a.b2 = b2; a.h1 = h1; a.h2 = h2; a.out = out; a.ldo = ldo;
-    const int kt0 = n_feat == 0 ? 4 : (k0 + 15) / 16, nto = n_out <= 16 ? 1 : 4;
-    const int kt0i = n_feat == 0 ? 4 : (kt0 <= 2 ? 2 : kt0);
-    const size_t lds = (size_t)(w3_units(4, (kt0i + 1) / 2) + w3_units(n_layers == 3 ? 4 : nto, 2) + (n_layers == 3 ? w3_units(nto, 2) : 0)) * 16 + 3 * 64 * sizeof(float);
     hipStream_t st = as_stream(stream);
-    const uint32_t grid = fused_grid(((n + 15) / 16 + kNeckChunk - 1) / kNeckChunk, kNThreads);
-    EMER_RMLP_DISPATCH(rmlp_fwd_kernel, a, lds, "rmlp_fwd");
+    const uint32_t grid = row_chunk_grid(n);
+    return dispatch_kt0_f<2, 0, 4>(k0, n_feat, [&](auto kt0, auto f) {
+        return dispatch_nl_nto(n_layers, n_out, [&](auto nl, auto nto) {
+            return launch(rmlp_fwd_kernel<RUNG(kt0), RUNG(f), RUNG(nl), RUNG(nto)>, grid, kNThreads, RMlpFwdLds<RUNG(kt0), RUNG(nl), RUNG(nto)>::bytes, st,
+                          "rmlp_fwd", a);
+        });
+    });
 }
 
 // Data-gradient chain of emer_rmlp_fwd.  dlast [n][ldd]: gradient at the last pre-activation (the caller applies
@@ -2822,29 +2816,26 @@ extern "C" int emer_rmlp_bwd(const float *dlast, int64_t ldd, const float *h1, c
     a.w1t = WSrc{w1, 1, 64, 64, 64};
     a.w0t = WSrc{w0, 1, k0, k0, 64};      // (n = input feature, k = hidden) = w0[k][n]
     a.dpre1 = dpre1; a.dpre0 = dpre0; a.dx = dx; a.lddx = lddx;
-    const int kt0 = n_feat == 0 ? 4 : (k0 + 15) / 16, nto = n_out <= 16 ? 1 : 4;
-    const int kt0i = n_feat == 0 ? 4 : (kt0 <= 2 ? 2 : kt0);
-    const size_t lds = (size_t)(w3_units(4, (nto + 1) / 2) + (n_layers == 3 ? w3_units(4, 2) : 0) + w3_units(kt0i, 2)) * 16;
     hipStream_t st = as_stream(stream);
-    const uint32_t grid = fused_grid((n + 15) / 16, kNThreads);
-    EMER_RMLP_DISPATCH(rmlp_bwd_kernel, a, lds, "rmlp_bwd");
+    const uint32_t grid = persistent_grid((n + 15) / 16, kNThreads / 64, 512);
+    return dispatch_kt0_f<2, 0, 4>(k0, n_feat, [&](auto kt0, auto f) {
+        return dispatch_nl_nto(n_layers, n_out, [&](auto nl, auto nto) {
+            return launch(rmlp_bwd_kernel<RUNG(kt0), RUNG(f), RUNG(nl), RUNG(nto)>, grid, kNThreads, RMlpBwdLds<RUNG(kt0), RUNG(nl), RUNG(nto)>::bytes, st,
+                          "rmlp_bwd", a);
+        });
+    });
 }
 
 // ---- plain 2- / 3-layer heads: backward with the weight gradients fused [r5] ------------------------------------------------
-static inline int rmlp_bwdw_nto(int n_out) { return n_out <= 16 ? 1 : 4; }
-static inline int rmlp_bwdw_threads(int n_layers, int n_out) { return (n_layers == 3 || rmlp_bwdw_nto(n_out) == 4) ? 256 : 512; }
+static constexpr int rmlp_bwdw_threads(int n_layers, int nto) { return (n_layers == 3 || nto == 4) ? 256 : 512; }   // (rmlp_w_threads<NL, NTO>)
 static inline uint32_t rmlp_bwdw_grid(int64_t n, int n_layers, int n_out) {
-    const int nw = rmlp_bwdw_threads(n_layers, n_out) / 64;
-    const int64_t tiles = (n + 15) / 16;
-    int64_t blocks = (tiles + nw - 1) / nw;
-    if (blocks > 256) blocks = 256;   // persistent: one workgroup per CU
-    return (uint32_t)(blocks < 1 ? 1 : blocks);
+    return persistent_grid((n + 15) / 16, rmlp_bwdw_threads(n_layers, rmlp_nto(n_out)) / 64, 256);   // one workgroup per CU
 }
 static inline int64_t rmlp_bwdw_stride(int n_layers, int k0, int n_out) {
     return ((int64_t)n_out * 65 + (n_layers == 3 ? 64 * 65 : 0) + 64 * (int64_t)k0 + 64 + 3) / 4 * 4;
 }
-static inline size_t rmlp_bwdw_lds(int n_layers, int kt0, int n_out) {
-    const int nw = rmlp_bwdw_threads(n_layers, n_out) / 64, nto = rmlp_bwdw_nto(n_out);
+static constexpr size_t rmlp_bwdw_lds(int n_layers, int kt0, int nto) {
+    const int nw = rmlp_bwdw_threads(n_layers, nto) / 64;
     const size_t w = (size_t)(w3_units(4, (kt0 + 1) / 2) + w3_units(4, (nto + 1) / 2) + w3_units(kt0, 2) + (n_layers == 3 ? 2 * w3_units(4, 2) : 0)) * 16
                      + (size_t)(128 + nw * 384 * kt0) * sizeof(float);
     const size_t r = (size_t)(16 * nto * 65 + (n_layers == 3 ? 64 * 64 + 64 : 0) + 64 * 16 * kt0 + 64) * sizeof(float);
@@ -2882,7 +2873,7 @@ extern "C" int emer_rmlp_bwd_fused(const float *dout, int64_t ldd, const float *
     EMER_REQUIRE(n_feat == 0 || (n_levels * n_feat == k0 && n * k0 < (1ll << 30)), "rmlp_bwd_fused: level-major input needs k0 == n_levels * n_feat and n * k0 < 2^30");
     EMER_REQUIRE(!dx || n_feat != 0 || (lddx >= k0 && lddx % 4 == 0 && ((uintptr_t)dx % 16) == 0), "rmlp_bwd_fused: row-major dx needs lddx %% 4 == 0 and 16-byte alignment");
     EMER_REQUIRE(ld_dw0 >= k0 && ld_dw1 >= 64 && (n_layers == 2 || ld_dw2 >= 64), "rmlp_bwd_fused: leading dimension smaller than the row");
-    const int nto = rmlp_bwdw_nto(n_out);
+    const int nto = rmlp_nto(n_out);
     EMER_REQUIRE(nto == 1 || (ldd % 4 == 0 && ((uintptr_t)dout % 16) == 0 && (final_act == EMER_ACT_NONE || (ldo % 4 == 0 && ((uintptr_t)out % 16) == 0))),
                  "rmlp_bwd_fused: wide outputs need 16-byte aligned rows of dout (and of out for a sigmoid)");
     RMlpBwdWArgs a;
@@ -2896,22 +2887,16 @@ extern "C" int emer_rmlp_bwd_fused(const float *dout, int64_t ldd, const float *
     a.w1t = WSrc{w1, 1, 64, 64, 64};
     a.w0t = WSrc{w0, 1, k0, k0, 64};      // (n = input feature, k = hidden) = w0[k][n]
     a.dx = dx; a.lddx = lddx; a.partials = workspace; a.stride = rmlp_bwdw_stride(n_layers, k0, n_out);
-    const int kt0 = n_feat == 0 ? 4 : ((k0 + 15) / 16 <= 2 ? 2 : (k0 + 15) / 16);
     const uint32_t grid = rmlp_bwdw_grid(n, n_layers, n_out);
-    const size_t lds = rmlp_bwdw_lds(n_layers, kt0, n_out);
-    const int threads = rmlp_bwdw_threads(n_layers, n_out);
     hipStream_t st = as_stream(stream);
-    int rc = EMER_E_INVALID;
-    auto go = [&](auto kern) {
-        if (int r = set_lds(kern, lds, "rmlp_bwd_fused")) return r;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
-        return check_launch("rmlp_bwd_fused");
+    auto go = [&](auto kt0, auto f, auto nl, auto nt) {
+        return launch(rmlp_bwdw_kernel<RUNG(kt0), RUNG(f), RUNG(nl), RUNG(nt)>, grid, rmlp_bwdw_threads(RUNG(nl), RUNG(nt)),
+                      rmlp_bwdw_lds(RUNG(nl), RUNG(kt0), RUNG(nt)), st, "rmlp_bwd_fused", a);
     };
-    if (nto == 4) rc = go(rmlp_bwdw_kernel<4, 0, 3, 4>);
-    else if (n_feat == 0) rc = n_layers == 2 ? go(rmlp_bwdw_kernel<4, 0, 2, 1>) : go(rmlp_bwdw_kernel<4, 0, 3, 1>);
-    else if (kt0 == 2) rc = n_layers == 2 ? go(rmlp_bwdw_kernel<2, 4, 2, 1>) : go(rmlp_bwdw_kernel<2, 4, 3, 1>);
-    else if (kt0 == 3) rc = n_layers == 2 ? go(rmlp_bwdw_kernel<3, 4, 2, 1>) : go(rmlp_bwdw_kernel<3, 4, 3, 1>);
-    else rc = n_layers == 2 ? go(rmlp_bwdw_kernel<4, 4, 2, 1>) : go(rmlp_bwdw_kernel<4, 4, 3, 1>);
+    // wide outputs: the feature heads only (three layers, row-major input); up to 16 outputs: every input rung, two or three layers
+    const int rc = nto == 4 ? go(I<4>{}, I<0>{}, I<3>{}, I<4>{}) : dispatch_kt0_f<2, 0, 4>(k0, n_feat, [&](auto kt0, auto f) {
+        return n_layers == 2 ? go(kt0, f, I<2>{}, I<1>{}) : go(kt0, f, I<3>{}, I<1>{});
+    });
     if (rc) return rc;
     DwReduceJob jb[3];
     int nj = 0;

@@ -420,7 +420,7 @@ def test_forwards_outside_autograd_recording_match(hip_lib):
     assert torch.equal(want, got) and not got.requires_grad
 
 
-@pytest.mark.parametrize("L,Fe,R,S", [(16, 2, 64, 32), (10, 4, 7, 16), (4, 2, 3, 128)])
+@pytest.mark.parametrize("L,Fe,R,S", [(16, 2, 64, 32), (10, 4, 7, 16), (4, 2, 3, 128), (16, 4, 3, 16)])   # kt0 = 2, 3, 1, 4
 def test_field_forward_rides_along(hip_lib, L, Fe, R, S):
     """emer_field_fwd (neck + rgb head in one launch, fused.RgbRider) against the two separate launches: geometry features,
     density and colour bit-identical; gradients of every parameter identical too (the backward is the separate kernels' in
@@ -467,6 +467,97 @@ def test_field_forward_rides_along(hip_lib, L, Fe, R, S):
         other = [w.clone() for w in ph]
         rgb = fused.rgb_head(hray, geo, S, *other)
     assert rgb.data_ptr() != rider.out.data_ptr() and torch.equal(rgb, rider.out)
+
+
+def test_hidden_stores_change_nothing_else(hip_lib):
+    """The forward kernels share their stages between the entry points whether or not the hidden activations are stored (h1 of the
+    neck, h1 / h2 of the plain heads, a1 / a2 of the rgb head: null when no backward will read them).  Through the C entry points at 33
+    rows and at R = 3, S = 16: with any of them null every other output is bitwise what the call with every pointer given writes."""
+    from tests import _head_calls as H
+
+    def same(tag, full, part, null):
+        for k, v in part.items():
+            if v is None:
+                assert k in null or full[k] is None, f"{tag}: {k}"
+                continue
+            assert torch.equal(v, full[k]), f"{tag} null={null}: {k} differs"
+            assert not (v == 7.5).all(), f"{tag} null={null}: {k} was not written"
+
+    for L, Fe, n_out in ((12, 2, 1), (16, 2, 64), (10, 4, 128)):
+        c = H.neck_case(L, Fe, n_out, 33)
+        same(f"neck_fwd n_out={n_out}", H.neck_fwd(c), H.neck_fwd(c, ("h1",)), ("h1",))
+    for n_layers in (2, 3):
+        for lm, k0 in ((False, 64), (True, 40)):
+            c = H.rmlp_case(n_layers, lm, k0, 6, 33)
+            full = H.rmlp_fwd(c)
+            for null in (("h1",), ("h2",), ("h1", "h2")) if n_layers == 3 else (("h1",),):
+                same(f"rmlp_fwd layers={n_layers} lm={lm}", full, H.rmlp_fwd(c, null), null)
+    c = H.rgb_case(3, 16, 49, 10, 4)
+    for fwd in (H.rgb_head_fwd, H.field_fwd):
+        full = fwd(c)
+        for null in (("a2",), ("a1", "a2")):
+            same(fwd.__name__, full, fwd(c, null), null)
+
+
+# One case per rung of the dispatch (tests/_head_calls.py builds nothing here: these go through emernerf_amd.fused).  L is the odd level count
+# whose L * F features end inside input tile kt0, so a rung wired to the wrong instantiation drops or pads features.
+NECK_RUNGS = [(L, Fe) for Fe, Ls in ((1, (13, 29, 45, 61)), (2, (7, 15, 23, 31)), (4, (3, 7, 11, 15)), (8, (1, 3, 5, 7))) for L in Ls]
+
+
+@pytest.mark.parametrize("fusedw", [False, True])   # emer_neck_bwd + streamed weight gradients / emer_neck_bwd_fused
+@pytest.mark.parametrize("L,Fe", NECK_RUNGS)
+def test_every_neck_rung(hip_lib, monkeypatch, L, Fe, fusedw):
+    """Every (KT0, F) rung of the neck's dispatch, forward and backward, at 33 rows, held by neck_bound."""
+    from emernerf_amd import fused
+    monkeypatch.setattr(fused, "FUSED_WGRAD", fusedw)
+    dev = torch.device("cuda:0")
+    N, NG, K0 = 33, 64, L * Fe
+    assert fused.neck_supported(L, Fe, 64, NG)
+    g = torch.Generator().manual_seed(100 * L + Fe)
+    enc = torch.randn(L, N, Fe, generator=g)
+    W0, b0 = torch.randn(64, K0, generator=g) / K0 ** 0.5, torch.randn(64, generator=g) * 0.1
+    W1, b1 = torch.randn(NG, 64, generator=g) / 8, torch.randn(NG, generator=g) * 0.1
+    gg, gd = torch.randn(N, NG, generator=g), torch.randn(N, generator=g)
+    t = [v.to(dev).requires_grad_(True) for v in (enc, W0, b0, W1, b1)]
+    geo, sem, dens = fused.neck(*t)
+    assert sem is None
+    ((geo * gg.to(dev)).sum() + (dens * gd.to(dev)).sum()).backward()
+    neck_bound(f"neck rung L{L}F{Fe} fusedw={fusedw}", enc.double().permute(1, 0, 2).reshape(N, K0), W0, b0, W1, b1, gg.double(), gd.double(),
+               {"feats": geo, "density": dens, "dx": _lm_rows(t[0].grad, N), "dW0": t[1].grad, "db0": t[2].grad, "dW1": t[3].grad, "db1": t[4].grad})
+
+
+# (layout, k0): row-major runs four input tiles whatever k0; level-major F = 4 with kt0 = 1 (runs the kt0 = 2 kernel), 2, 3, 4
+RMLP_RUNGS = [("rm", 44), ("lm", 8), ("lm", 28), ("lm", 44), ("lm", 60)]
+
+
+@pytest.mark.parametrize("n_out", [6, 24])          # NTO = 1 / 4 output tiles
+@pytest.mark.parametrize("n_layers", [2, 3])
+@pytest.mark.parametrize("layout,k0", RMLP_RUNGS)
+def test_every_plain_head_rung(hip_lib, layout, k0, n_layers, n_out, rmlp_wgrad_mode):
+    """Every (layout, kt0, NL, NTO) rung of the plain heads' dispatch, forward and backward, at 33 rows, held by stack_bound."""
+    from emernerf_amd import fused
+    dev = torch.device("cuda:0")
+    N = 33
+    g = torch.Generator().manual_seed(1000 * k0 + 10 * n_layers + n_out)
+    widths = (k0,) + (64,) * (n_layers - 1) + (n_out,)
+    x = torch.randn(k0 // 4, N, 4, generator=g) if layout == "lm" else torch.randn(N, k0, generator=g)
+    Ws = [torch.randn(widths[i + 1], widths[i], generator=g) / widths[i] ** 0.5 for i in range(n_layers)]
+    Bs = [torch.randn(widths[i + 1], generator=g) * 0.1 for i in range(n_layers)]
+    w = torch.randn(N, n_out, generator=g)
+    t = [v.to(dev).requires_grad_(True) for v in [x] + Ws + Bs]
+    if layout == "lm":
+        assert fused.rmlp_supported(Ws, k0, 4)
+        out = fused.seq_mlp_lm(t[0], t[1:1 + n_layers], t[1 + n_layers:])
+        x64, dx = x.double().permute(1, 0, 2).reshape(N, k0), lambda: _lm_rows(t[0].grad, N)
+    else:
+        assert fused.rmlp_supported(Ws, k0, 0)
+        out = fused.seq_mlp(t[0], t[1:1 + n_layers], t[1 + n_layers:])
+        x64, dx = x.double(), lambda: t[0].grad
+    (out * w.to(dev)).sum().backward()
+    got = {"out": out, "dx": dx()}
+    got.update({f"dW{i}": t[1 + i].grad for i in range(n_layers)})
+    got.update({f"db{i}": t[1 + n_layers + i].grad for i in range(n_layers)})
+    stack_bound(f"plain head rung {layout} k0={k0} layers={n_layers} n_out={n_out} fusedw={rmlp_wgrad_mode}", x64, Ws, Bs, False, w.double(), got)
 
 
 # ------------------------------------------------------------------------------------------ per-entry bounds (tests/_bounds.py)

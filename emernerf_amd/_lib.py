@@ -141,6 +141,9 @@ SIGNATURES = {
     "emer_pixel_error_normalise": [_P, c_int64, _P, c_int32, _P],
     "emer_ssim": [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P],
     "emer_sq_err_sums": [_P, _P, _P, c_int64, c_int32, _P, _P, _P],
+    "emer_feature_colours": [_P, c_int32, c_int64, c_int32, _P],
+    "emer_blend_over": [_P, c_int32, c_int64, _P],
+    "emer_flow_colours": [_P, c_int32, c_int64, _P, c_float, c_int32, _P],
     "emer_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_int32, _P],
 }
 

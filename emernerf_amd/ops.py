@@ -1332,3 +1332,161 @@ def sq_err_sums(pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, out
         ws = torch.empty(max(int(_lib.load().emer_sq_err_sums_workspace(rows, cols)), 1), dtype=torch.float64, device=p.device)
         _lib.call("emer_sq_err_sums", _ptr(p), _ptr(t), _ptr(m), rows, cols, _ptr(ws), _ptr(res), _stream(p))
     return res
+
+
+# ------------------------------------------------------------------------------------ evaluation colours
+COLOUR_JOBS_MAX = 8
+_TRANSITIONS = (15, 6, 4, 11, 13, 6)
+_WHEELS: dict = {}
+
+
+def colour_wheel():
+    """The cyclic flow colour wheel as a [56, 3] float32 numpy array (no GPU needed): the six hue transitions red -> yellow ->
+    green -> cyan -> blue -> magenta -> red of lengths (15, 6, 4, 11, 13, 6), each ``linspace(from, to, length,
+    endpoint=False)`` truncated to uint8, and the first row repeated at the end so that interpolation can wrap."""
+    import numpy as np
+    hues = [(255, 0, 0), (255, 255, 0), (0, 255, 0), (0, 255, 255), (0, 0, 255), (255, 0, 255), (255, 0, 0)]
+    wheel = np.zeros((sum(_TRANSITIONS), 3), dtype=np.uint8)
+    start = 0
+    for a, b, n in zip(hues[:-1], hues[1:], _TRANSITIONS):
+        wheel[start:start + n] = np.linspace(np.array(a), np.array(b), n, endpoint=False)
+        start += n
+    return np.concatenate([wheel, wheel[:1]]).astype(np.float32)
+
+
+def _wheel_on(device) -> Tensor:
+    w = _WHEELS.get(device)
+    if w is None:
+        w = _WHEELS[device] = torch.from_numpy(colour_wheel()).to(device)
+    return w
+
+
+class _FeatJob(ctypes.Structure):
+    """emer_feature_colour_job of include/emernerf_hip.h."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("feat", "mat", "lo", "hi", "scale", "out")]
+
+
+class _BlendJob(ctypes.Structure):
+    """emer_blend_over_job."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("a", "o", "b", "out")]
+
+
+class _FlowJob(ctypes.Structure):
+    """emer_flow_colour_job."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("flow", "out")]
+
+
+def _rows(t: Tensor, cols: int, what: str) -> Tensor:
+    """[..., cols] -> contiguous fp32 [rows, cols] (a contiguous fp32 input is a view: no copy)."""
+    if t.dim() < 1 or t.shape[-1] != cols:
+        raise _lib.EmerError(f"{what}: expected [..., {cols}], got {tuple(t.shape)}")
+    return _f32c(t).reshape(-1, cols)
+
+
+def _per_row(t: Tensor, rows: int, what: str) -> Tensor:
+    if t.numel() != rows:
+        raise _lib.EmerError(f"{what}: {t.numel()} elements for {rows} rows")
+    return _f32c(t).reshape(rows)
+
+
+def feature_colours_multi(jobs):
+    """Several PCA-colour projections of one image as ONE launch (emer_feature_colours): ``jobs`` is a list of
+    ``(feat [..., E], mat [E, 3], lo [3], hi [3], scale [...] | None)`` with one row count and one E; returns the list of
+    ``clamp((feat @ mat - lo) / (hi - lo), 0, 1) [* scale]`` of shape [..., 3].  A true subtraction and division, torch's clamp
+    (NaN stays NaN); a row's value does not depend on the other rows or members.  Not differentiable: call under no_grad."""
+    if not 1 <= len(jobs) <= COLOUR_JOBS_MAX:
+        raise _lib.EmerError(f"feature_colours: 1..{COLOUR_JOBS_MAX} jobs, got {len(jobs)}")
+    E = jobs[0][0].shape[-1]
+    arr, keep, outs = (_FeatJob * len(jobs))(), [], []
+    n_rows = None
+    for i, (feat, mat, lo, hi, scale) in enumerate(jobs):
+        _check_cuda(feat, mat, lo, hi, scale)
+        f = _rows(feat, E, "feature_colours: feat")
+        if n_rows is None:
+            n_rows = f.shape[0]
+        if f.shape[0] != n_rows:
+            raise _lib.EmerError("feature_colours: the jobs of one launch share the row count")
+        if tuple(mat.shape) != (E, 3) or lo.numel() != 3 or hi.numel() != 3:
+            raise _lib.EmerError(f"feature_colours: need mat [{E}, 3], lo [3], hi [3]; got {tuple(mat.shape)}, {tuple(lo.shape)}, {tuple(hi.shape)}")
+        m, l, h = _f32c(mat).to(f.device), _f32c(lo).reshape(3).to(f.device), _f32c(hi).reshape(3).to(f.device)
+        s = None if scale is None else _per_row(scale, n_rows, "feature_colours: scale")
+        out = _empty(f, *feat.shape[:-1], 3)
+        keep.append((f, m, l, h, s))
+        outs.append(out)
+        arr[i] = _FeatJob(f.data_ptr(), m.data_ptr(), l.data_ptr(), h.data_ptr(), None if s is None else s.data_ptr(), out.data_ptr())
+    ref = keep[0][0]
+    with torch.cuda.device(ref.device):
+        _lib.call("emer_feature_colours", arr, len(jobs), n_rows, E, _stream(ref))
+    return outs
+
+
+def feature_colours(feat: Tensor, mat: Tensor, lo: Tensor, hi: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+    """``clamp((feat @ mat - lo) / (hi - lo), 0, 1) [* scale]``: [..., E] features to [..., 3] colours (see
+    ``feature_colours_multi``)."""
+    return feature_colours_multi([(feat, mat, lo, hi, scale)])[0]
+
+
+def blend_over_multi(jobs):
+    """Several over-blends of one image as ONE launch (emer_blend_over): ``jobs`` is a list of ``(a [..., 3], o [...], b [..., 3])``;
+    returns the list of ``clip(a * o + b * (1 - o), 0, 1)``, every operation rounded on its own as numpy evaluates it."""
+    if not 1 <= len(jobs) <= COLOUR_JOBS_MAX:
+        raise _lib.EmerError(f"blend_over: 1..{COLOUR_JOBS_MAX} jobs, got {len(jobs)}")
+    arr, keep, outs = (_BlendJob * len(jobs))(), [], []
+    n_rows = None
+    for i, (a, o, b) in enumerate(jobs):
+        _check_cuda(a, o, b)
+        x, y = _rows(a, 3, "blend_over: a"), _rows(b, 3, "blend_over: b")
+        if n_rows is None:
+            n_rows = x.shape[0]
+        if x.shape[0] != n_rows or y.shape[0] != n_rows:
+            raise _lib.EmerError("blend_over: a, b and the jobs of one launch share the row count")
+        w = _per_row(o, n_rows, "blend_over: o")
+        out = _empty(x, *a.shape[:-1], 3)
+        keep.append((x, y, w))
+        outs.append(out)
+        arr[i] = _BlendJob(x.data_ptr(), w.data_ptr(), y.data_ptr(), out.data_ptr())
+    ref = keep[0][0]
+    with torch.cuda.device(ref.device):
+        _lib.call("emer_blend_over", arr, len(jobs), n_rows, _stream(ref))
+    return outs
+
+
+def blend_over(a: Tensor, o: Tensor, b: Tensor) -> Tensor:
+    """``clip(a * o + b * (1 - o), 0, 1)`` for [..., 3] ``a``, ``b`` and a per-row ``o`` (see ``blend_over_multi``)."""
+    return blend_over_multi([(a, o, b)])[0]
+
+
+def flow_colours_multi(flows, max_radius: Optional[float] = 1.0, background: str = "bright"):
+    """The colour-wheel images of several [..., 3] flows of one shape as ONE launch (emer_flow_colours): the reference's
+    ``scene_flow_to_rgb`` (hue from the angle of (x, y) by linear interpolation on the 55-step wheel, saturation ("bright") or
+    value ("dark") from the radius / max_radius, the other axis beyond radius 1), in [0, 1].  ``max_radius=None`` (the
+    reference's 99 % quantile rule) is not implemented."""
+    if max_radius is None:
+        raise NotImplementedError("flow_colours: max_radius=None (the quantile rule) is not implemented; pass a radius")
+    if background not in ("bright", "dark"):
+        raise ValueError(f"background should be one the following: ('bright', 'dark'), not {background}.")
+    if not 1 <= len(flows) <= COLOUR_JOBS_MAX:
+        raise _lib.EmerError(f"flow_colours: 1..{COLOUR_JOBS_MAX} flows, got {len(flows)}")
+    arr, keep, outs = (_FlowJob * len(flows))(), [], []
+    n_rows = None
+    for i, flow in enumerate(flows):
+        _check_cuda(flow)
+        f = _rows(flow, 3, "flow_colours: flow")
+        if n_rows is None:
+            n_rows = f.shape[0]
+        if f.shape[0] != n_rows:
+            raise _lib.EmerError("flow_colours: the flows of one launch share the row count")
+        out = _empty(f, *flow.shape[:-1], 3)
+        keep.append(f)
+        outs.append(out)
+        arr[i] = _FlowJob(f.data_ptr(), out.data_ptr())
+    ref = keep[0]
+    with torch.cuda.device(ref.device):
+        _lib.call("emer_flow_colours", arr, len(flows), n_rows, _ptr(_wheel_on(ref.device)), float(max_radius),
+                  1 if background == "dark" else 0, _stream(ref))
+    return outs
+
+
+def flow_colours(flow: Tensor, max_radius: Optional[float] = 1.0, background: str = "bright") -> Tensor:
+    """``scene_flow_to_rgb(flow, flow_max_radius=max_radius, background=background)`` on the device (see ``flow_colours_multi``)."""
+    return flow_colours_multi([flow], max_radius, background)[0]

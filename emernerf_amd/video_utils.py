@@ -11,7 +11,14 @@ the next image's rendering (the reference interleaves a blocking ``.cpu().numpy(
 metrics -- PSNR, SSIM (scikit-image's algorithm, csrc/metrics.hip), feature PSNR and their dynamic-mask variants -- are
 computed on the device and read back once after the loop.  ``cache_pixel_error_maps`` is the training loop's periodic
 refresh of the importance sampler's error buffer (train_emernerf.py:879-904): a low-resolution pass over the full set whose
-results never leave the GPU.  Out of scope here: video encoding, DINO-feature PCA colouring.
+results never leave the GPU.
+
+``visualize=True`` adds the reference's pictures (video_utils.py:184-187,233-418): ``forward_flows`` / ``backward_flows`` become the
+colour-wheel images and a feature model's DINO lists (``dino_feats``, ``gt_dino_feats``, ``dino_feats_pe_free``, ``dino_pe``,
+``static_dino_feats``, ``dynamic_dino_feats`` and the two cross blends) are produced from the E-wide feature images by the
+kernels of csrc/colours.hip: at most two launches per image for all feature lists, one for the flows; only [H, W, 3] colours
+join the image's transfer.  ``get_robust_pca`` is the reference's robust PCA colour rule (utils/misc.py:23-47) made
+deterministic.  Out of scope here: video encoding, the turbo depth colouring of ``save_videos``, ``resize_five_views``.
 """
 from __future__ import annotations
 
@@ -74,12 +81,13 @@ def _unpack(item, out: Dict[str, list]) -> None:
 
 def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimator, dataset,
                   proposal_networks: Optional[List[DensityField]] = None, compute_metrics: bool = False,
-                  vis_indices: Optional[List[int]] = None, return_decomposition: bool = True) -> Dict[str, list]:
+                  vis_indices: Optional[List[int]] = None, return_decomposition: bool = True, visualize: bool = False,
+                  feature_pca: Optional[dict] = None) -> Dict[str, list]:
     """video_utils.py:50-106.  ``dataset``: anything with ``__len__`` / ``__getitem__`` returning image-shaped ray dicts
     (``PixelSource`` here; the reference's SplitWrapper there).  Nothing here or in ``render`` depends on the image size: with
     ``PixelSource.update_downscale_factor(1 / k)`` set, the same loop is the reference's low-resolution preview pass
     (train_emernerf.py:290-302) on [floor(H / k), floor(W / k)] images; previews smaller than 7 x 7 fall under ``render``'s
-    SSIM rule."""
+    SSIM rule.  ``visualize`` / ``feature_pca``: see ``render``."""
     model.eval()
     for p in proposal_networks or []:
         p.eval()
@@ -90,7 +98,8 @@ def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimato
         return render_rays(radiance_field=model, proposal_estimator=proposal_estimator, proposal_networks=proposal_networks,
                            data_dict=data_dict, cfg=cfg, return_decomposition=return_decomposition)
 
-    results = render(dataset, render_func, model=model, compute_metrics=compute_metrics, vis_indices=vis_indices)
+    results = render(dataset, render_func, model=model, compute_metrics=compute_metrics, vis_indices=vis_indices, visualize=visualize,
+                     feature_pca=feature_pca)
     if compute_metrics:
         n = len(dataset) if vis_indices is None else len(vis_indices)
         logger.info(f"Eval over {n} images:")
@@ -132,8 +141,80 @@ def cache_pixel_error_maps(cfg, model: RadianceField, proposal_estimator: PropNe
             m.train(training)
 
 
+def get_robust_pca(features: Tensor, m: float = 2.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """utils/misc.py:23-47 (remove_first_component=False), deterministic: (reduction matrix [E, 3], colour min [3], colour max
+    [3]) of [N, E] features.  The matrix holds the three leading principal axes of the CENTRED features -- the top eigenvectors
+    of the E x E covariance (float64 ``torch.linalg.eigh`` on the host: it runs once per loop), each column's sign fixed so that
+    its largest-magnitude entry is positive -- where the reference's ``torch.pca_lowrank`` is randomised (same subspace, not the
+    same digits).  The colours are the UNCENTRED product ``features @ matrix``; min and max per channel run over the rows whose
+    absolute deviation from the channel's median is below ``m`` times the median absolute deviation.  Plain torch: works on CPU
+    and device tensors."""
+    assert features.dim() == 2 and features.shape[1] >= 3, "features should be (N, C) with C >= 3"
+    x = features.detach().to(torch.float64)
+    xc = x - x.mean(dim=0, keepdim=True)
+    _, vecs = torch.linalg.eigh((xc.T @ xc).cpu())          # eigenvalues ascending
+    v = vecs[:, [-1, -2, -3]]
+    top = v.abs().argmax(dim=0)
+    v = v * torch.sign(v[top, torch.arange(3)])
+    mat = v.to(device=features.device, dtype=features.dtype)
+    colors = features.detach() @ mat
+    d = torch.abs(colors - torch.median(colors, dim=0).values)
+    s = d / torch.median(d, dim=0).values
+    lo = torch.stack([colors[s[:, c] < m, c].min() for c in range(3)])
+    hi = torch.stack([colors[s[:, c] < m, c].max() for c in range(3)])
+    return mat, lo.to(mat), hi.to(mat)
+
+
+_FEATURE_LISTS = ["dino_feats", "gt_dino_feats", "dino_feats_pe_free", "dino_pe", "static_dino_feats", "dynamic_dino_feats",
+                  "dynamic_dino_on_static_rgbs", "dynamic_rgb_on_static_dinos"]
+
+
+def _feature_colour_lists(res: Dict[str, Tensor], data: Dict[str, Tensor], model, pca: Optional[dict]):
+    """The reference's DINO colour lists of one image (video_utils.py:233-418), quirks included, as ({list name: [H, W, 3]
+    colours}, pca): ONE launch for every projection (per feature width), ONE for the two cross blends.  ``pca``: the PE-free / PE
+    matrices; computed here from this image when None and the results carry ``dino_pe_free`` (:273-301)."""
+    if model is None:
+        raise ValueError("render(visualize=True): the feature colours need `model` (its registered feats_reduction_mat / feat_color_min / feat_color_max)")
+    feat = res["dino_feat"]
+    reg = (model.feats_reduction_mat, model.feat_color_min, model.feat_color_max)
+    jobs = [("dino_feats", feat, reg, None)]                     # no opacity multiply (:413-415)
+    if "features" in data:
+        jobs.append(("gt_dino_feats", data["features"], reg, None))
+    if "dino_pe_free" in res:
+        if pca is None:
+            E = res["dino_pe_free"].shape[-1]
+            non_sky = res["dino_pe_free"] * (~data["sky_masks"].bool().unsqueeze(-1)).to(res["dino_pe_free"])
+            pca = {"pe_free": get_robust_pca(non_sky.reshape(-1, E), m=2.5), "pe": get_robust_pca(res["dino_pe"].reshape(-1, E), m=2.5)}
+        free = tuple(t.to(feat.device) for t in pca["pe_free"])
+        jobs.append(("dino_feats_pe_free", res["dino_pe_free"], free, res["opacity"]))
+        jobs.append(("dino_pe", res["dino_pe"], tuple(t.to(feat.device) for t in pca["pe"]), None))
+        if "static_dino" in res:
+            jobs.append(("static_dino_feats", res["static_dino"], free, None))
+        if "dynamic_dino" in res:
+            jobs.append(("dynamic_dino_feats", res["dynamic_dino"], free, res["dynamic_opacity"]))
+    else:
+        if "static_dino" in res:
+            jobs.append(("static_dino_feats", res["static_dino"], reg, None))
+        if "dynamic_dino" in res:
+            jobs.append(("dynamic_dino_feats", res["dynamic_dino"], reg, None))    # no opacity multiply in this branch (:400-401)
+    cols: Dict[str, Tensor] = {}
+    for E in sorted({j[1].shape[-1] for j in jobs}):             # one launch (ground-truth features of another width: one more)
+        part = [j for j in jobs if j[1].shape[-1] == E]
+        for (name, *_), c in zip(part, ops.feature_colours_multi([(f, *p, s) for _, f, p, s in part])):
+            cols[name] = c
+    blends = []
+    if "static_dino_feats" in cols:       # dynamic rgb over the static feature colours (:334-342, :381-389)
+        blends.append(("dynamic_rgb_on_static_dinos", res["dynamic_rgb"], res["dynamic_opacity"], cols["static_dino_feats"]))
+    if "dynamic_dino_feats" in cols:      # in the PE branch the dynamic colours carry dynamic_opacity already: it applies twice (:355-362)
+        blends.append(("dynamic_dino_on_static_rgbs", cols["dynamic_dino_feats"], res["dynamic_opacity"], res["static_rgb"]))
+    if blends:
+        for (name, *_), c in zip(blends, ops.blend_over_multi([b[1:] for b in blends])):
+            cols[name] = c
+    return cols, pca
+
+
 def render(dataset, render_func: Callable, model: Optional[RadianceField] = None, compute_metrics: bool = False,
-           vis_indices: Optional[List[int]] = None) -> Dict[str, list]:
+           vis_indices: Optional[List[int]] = None, visualize: bool = False, feature_pca: Optional[dict] = None) -> Dict[str, list]:
     """video_utils.py:109-468: the reference's result dictionary key for key -- the nine lists it always returns (possibly
     empty), the conditional ones (gt_rgbs, gt_sky_masks, shadow_*, forward_flows / backward_flows, median_depths), the
     scalars psnr, ssim, feat_psnr, masked_psnr, masked_ssim, masked_feat_psnr under the reference's rules (:206-247,421-428):
@@ -141,13 +222,26 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
     masked_feat_psnr only where the results carry ``dino_feat`` and the data ``features``; each the mean over the images that
     contributed, -1 when none did, and all -1 when ``compute_metrics`` is False.  Per-image values stay in a device tensor
     and are read back once, after the loop.  One deliberate deviation: an image smaller than 7 x 7 is left out of ssim /
-    masked_ssim (a warning is logged once), where scikit-image raises.  The DINO-feature PCA colouring lists are not
-    produced.  ``forward_flows`` / ``backward_flows`` hold the rendered flow (the reference stores its colour-wheel
-    visualisation).  Checked against recordings of the reference's own loop: tests/golden/render_pixels_*.npz."""
+    masked_ssim (a warning is logged once), where scikit-image raises.  Checked against recordings of the reference's own
+    loop: tests/golden/render_pixels_*.npz.
+
+    ``visualize=False`` (the default): ``forward_flows`` / ``backward_flows`` hold the rendered flow and no DINO colour list
+    is produced.  ``visualize=True`` is the reference's picture output: the flow lists hold ``ops.flow_colours(flow, 1.0,
+    "bright")`` (:35-43,184-187), and where the results carry ``dino_feat`` the loop returns ``dino_feats``, ``gt_dino_feats``
+    (data with ``features``), and -- under the reference's conditions, names and quirks (:233-418,442-457) --
+    ``dino_feats_pe_free``, ``dino_pe``, ``static_dino_feats``, ``dynamic_dino_feats``, ``dynamic_rgb_on_static_dinos``,
+    ``dynamic_dino_on_static_rgbs``.  The PE-free / PE colour matrices come from ``feature_pca`` ({"pe_free": (mat [E, 3],
+    lo [3], hi [3]), "pe": (...)}) or, when None, from the first rendered image by ``get_robust_pca`` (sky zeroed, m = 2.5);
+    they are returned under ``feature_pca`` so that a later call can colour another split consistently.  ``get_robust_pca`` is
+    deterministic where the reference's ``torch.pca_lowrank`` is randomised: the colours follow the reference's formulas for
+    the same matrices, not its random draw.  Checked against tests/golden/flow_colours.npz / feature_colours.npz."""
     always = ["rgbs", "static_rgbs", "dynamic_rgbs", "depths", "opacities", "static_depths", "static_opacities", "dynamic_depths",
               "dynamic_opacities"]
     out: Dict[str, list] = {v: [] for v in _COLLECT.values()}
     out.update({"gt_rgbs": [], "dynamic_rgbs": [], "median_depths": [], "gt_sky_masks": []})
+    if visualize:
+        out.update({k: [] for k in _FEATURE_LISTS})
+    pca = feature_pca
     psnrs: List[Tensor] = []
     pending: list = []
     pinned: Dict[int, Tensor] = {}
@@ -180,6 +274,14 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
                 keep["gt_rgbs"] = data["pixels"]
             if "sky_masks" in data:
                 keep["gt_sky_masks"] = data["sky_masks"]
+            if visualize:
+                flows = [k for k in ("forward_flow", "backward_flow") if k in res]
+                if flows:  # both directions of the image in one launch (:184-187)
+                    for k, c in zip(flows, ops.flow_colours_multi([res[k] for k in flows], 1.0, "bright")):
+                        keep[_COLLECT[k]] = c
+                if "dino_feat" in res:
+                    cols, pca = _feature_colour_lists(res, data, model, pca)
+                    keep.update(cols)
             if compute_metrics and "pixels" in data:  # stays on the device until the loop is over (no sync per image)
                 psnrs.append(-10.0 * torch.log10(torch.nn.functional.mse_loss(res["rgb"], data["pixels"])))
                 if metrics is None:
@@ -221,6 +323,8 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
     out = {k: v for k, v in out.items() if len(v) > 0 or k in always}
     dt = time.perf_counter() - t0
     out["render_rays_per_s"] = n_rays / dt if dt > 0 else float("nan")
+    if visualize and pca is not None:
+        out["feature_pca"] = pca
     out["psnr"] = (float(host[0]) if psnrs else -1.0) if compute_metrics else -1
     ssims, masked_ssims, masked_psnrs, feat_psnrs, masked_feat_psnrs = [], [], [], [], []
     if metrics is not None:

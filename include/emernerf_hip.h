@@ -873,6 +873,35 @@ int emer_sq_err_sums(const float *pred, const float *target, const float *row_ma
                      double *workspace, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation colours (radiance_fields/video_utils.py:233-418, utils/visualization_tools.py:204-275): the PCA colours of
+ * the E-wide feature images, the over-blends built from them and the flow colour wheel.  Each entry point runs up to
+ * EMER_COLOUR_JOBS_MAX members that share the row count as ONE launch.  No atomics; a row's result does not depend on the
+ * row count, the number of members or the grid.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMER_COLOUR_JOBS_MAX 8
+#define EMER_WHEEL_ROWS 56
+/* out[r][c] = clamp((sum_e feat[r][e] mat[e][c] - lo[c]) / (hi[c] - lo[c]), 0, 1) [* scale[r]] for c < 3: a true subtraction and
+ * a true division, the clamp of torch.clamp (NaN stays NaN).  feat [n_rows][n_feat] contiguous, mat [n_feat][3], lo / hi [3],
+ * scale [n_rows] or NULL, out [n_rows][3], all fp32.  The sum over e has a fixed order given by n_feat alone: 16-byte loads
+ * when n_feat % 4 == 0 and feat is 16-byte aligned, scalar loads otherwise, bit-identical results either way. */
+typedef struct emer_feature_colour_job {
+    const float *feat, *mat, *lo, *hi, *scale; float *out;
+} emer_feature_colour_job;
+int emer_feature_colours(const emer_feature_colour_job *jobs, int32_t n_jobs, int64_t n_rows, int32_t n_feat, void *stream);
+/* out[r][c] = clip(a[r][c] * o[r] + b[r][c] * (1 - o[r]), 0, 1), each operation rounded on its own (numpy's order). */
+typedef struct emer_blend_over_job {
+    const float *a, *o, *b; float *out;
+} emer_blend_over_job;
+int emer_blend_over(const emer_blend_over_job *jobs, int32_t n_jobs, int64_t n_rows, void *stream);
+/* scene_flow_to_rgb for a fixed max_radius: flow [n_rows][3] (x and y are used) -> out [n_rows][3] in [0, 1].  wheel:
+ * EMER_WHEEL_ROWS x 3 fp32 on the device (the cyclic colour wheel, first row repeated at the end). */
+typedef struct emer_flow_colour_job {
+    const float *flow; float *out;
+} emer_flow_colour_job;
+int emer_flow_colours(const emer_flow_colour_job *jobs, int32_t n_jobs, int64_t n_rows, const float *wheel, float max_radius,
+                      int32_t dark_background, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam as configured in builders.py:50-60,114-120: eps 1e-15,
  * betas (0.9, 0.99), weight_decay as L2) over one flat fp32 buffer; grad_scale multiplies the
  * gradient first (1/world_size after the RCCL all-reduce; GradScaler quirk).

@@ -423,7 +423,15 @@ extern "C" int emer_lidar_sample_rays(const uint64_t *seed_word, uint64_t salt, 
     return check_launch("lidar_sample_rays");
 }
 
-// workspace: 4 + 2048 u32 words
+// workspace: 4 + 2048 u32 words (reset by the first launch: it may hold anything).  flat_out receives the k winners in the order
+// the emit pass's atomic cursors hand out, not sorted.  k beyond the number of finite keys fills up with entries of key +inf.
+// Key +inf is shared by the weights that are not positive (zero, negative, NaN) and by positive weights so small that
+// -logf(u) / w overflows: w < 24 ln 2 / FLT_MAX = 4.9e-38, subnormals and the two lowest binades of the normal range.  Such a
+// weight counts as support in PixelSource.sample_important_rays but is drawn like a zero weight.  The normalised error map
+// (e - lo) / (hi - lo) with hi - lo <= 5 holds one only where a cell's mean |gt - pred| lies within 2.4e-37 of the minimum
+// without being equal to it, i.e. a rendered colour that agrees with an 8-bit ground truth to 37 decimals in all three
+// channels yet not exactly; the arithmetic does not exclude it (a sigmoid output below 1e-37 against a black pixel), nothing
+// rendered has produced it, and it only matters when k reaches the size of the support.
 extern "C" int emer_sample_importance(const float *weights, int64_t n_weights, const uint64_t *seed_word, uint64_t salt, int64_t k,
                                       uint32_t *workspace, int64_t *flat_out, void *stream) {
     EMER_REQUIRE(n_weights >= 1 && k >= 0 && k <= n_weights && k < (1ll << 31), "sample_importance: need 0 <= k <= n_weights");

@@ -452,6 +452,18 @@ __device__ __forceinline__ void set_row(uint64_t (&mask)[Q], uint32_t row) {
     for (int q = 0; q < Q; ++q) mask[q] |= ((row >> 6) == (uint32_t)q) ? b : 0ull;
 }
 
+// acc + w * v of the in-flight pair path, rounded as the per-combination loop it replaces was compiled: a fused multiply-add, except
+// that for two features the two terms of the last combination were a rounded product and a sum.  Pinned, so that the encoding stays
+// bitwise what it was whatever the compiler would contract in the new shape.
+__device__ __forceinline__ float pair_term(bool fused, float w, float v, float acc) {
+#pragma clang fp contract(off)
+    if (fused) return __builtin_fmaf(w, v, acc);
+    const float prod = w * v;
+    return acc + prod;
+}
+// The instantiations whose pair path issues the gathers of all (y, z[, t]) combinations before it consumes any (see the kernel).
+template <int D, int F, typename PT> constexpr bool pair_in_flight() { return sizeof(PT) == 4 && F <= 2 && D <= 3; }
+
 // ------------------------------------------------------------------------------------ forward
 // JAC [r4]: rows n >= jac_row0 also store J[f][d] = d out[n][level][f] / d x[n][d] (jac[level][n - jac_row0][F][D]) -- the corner
 // values are in registers here anyway, and the input gradient of the flow configs becomes a streaming contraction of J with dOut
@@ -494,18 +506,84 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
         // profiles/r06_pair16.txt).  The Jacobian forward keeps the generic loop: paired it needs 130 registers, three waves per SIMD
         // instead of four, and loses what the pairs gain (448 vs 437 us; forced to 128 registers it spills: 575 us).
         if constexpr ((sizeof(PT) * F <= 8 || (sizeof(PT) == 4 && F == 4)) && !JAC) {
-        if (li.hashed && pow2) {  // level-uniform
+        // (level-uniform; the buffer loads of the in-flight form take 32-bit byte offsets: a level of 2^31 bytes or more takes the generic loop)
+        if (li.hashed && pow2 && (!pair_in_flight<D, F, PT>() || li.size <= 0x7FFFFFFFu / (F * sizeof(PT)))) {
             paired = true;
             // Hashed power-of-two level: the x-neighbours of a (y, z[, t]) combination are idx0 = (x ^ h) & mask and
-            // idx1 = ((x+1) ^ h) & mask.  For even x they are the two halves of ONE aligned entry pair {2k, 2k+1}:
-            // a single double-width gather fetches both (a quarter fewer L1/TA lane requests on these levels).
-            // Accumulation order is unchanged (corner-major, x fastest).
+            // idx1 = ((x+1) ^ h) & mask.  For even x they are the two halves of ONE aligned entry pair {2k, 2k+1}, and one
+            // double-width gather fetches both (a quarter fewer L1/TA lane requests on these levels).  Accumulation order is
+            // unchanged (corner-major, x fastest).  Two forms:
+            //  * in flight (fp32 tables, F = 1 and 2, D <= 3: the main and the proposal table).  Every lane issues the SAME two loads per
+            //    combination -- A, double-width, at the aligned pair that holds idx0; B, one entry, at idx1, which even-x lanes silence -- and
+            //    the loads of all combinations go out before anything is consumed: eight gathers back to back, then vmcnt(7) .. (0).
+            //    A per-lane branch on the parity of x (the other form) runs both sides in practically every wave, each a load-and-wait:
+            //    four memory round trips one after the other.  Same session, 1 M training samples: main table 231.4 -> 214.8 us (199.5 ->
+            //    183.2 without bitmaps), proposal table 106.7 -> 100.5 us, SQ_WAIT_ANY / SQ_WAVE_CYCLES 0.69 -> 0.37 and 0.56 -> 0.35; in
+            //    the static step the main launch 263 -> 247 us, the step -10 us (profiles/grid_fwd_pairs_ab.json).  Even lanes silence B
+            //    with a buffer offset past the level (zeros, no fetch); loading A's address again with plain loads cost 10 registers
+            //    and lost on the proposal table (108.4 us).
+            //  * per combination (all other paired instantiations): the parent form.  The in-flight form was NOT measured for them.  Compiled only: D4 with
+            //    F = 2 goes from 64 to 78 registers (8 waves -> 6; with 256 bitmap rows 62 -> 84, 8 -> 5), a prototype for F = 4 fp32
+            //    lost a wave as well (D3: 62 -> 66 registers, D4: 96 -> 128), and fp16 entries of 2 bytes would need a 16-bit load B.
+            //    They take the other form only after an A/B of their own.
             const uint32_t primes[4] = {1u, 2654435761u, 805459861u, 3674653429u};
             const uint32_t maskv = li.size - 1u;
             const bool x_even = (gi[0] & 1u) == 0u;
             // inside the grid (gi[0] + 1 <= res) the two x-neighbours differ only in index bits below the slice bits when
             // the resolution is below the slice width: one membership bit covers both
             const bool x_pair_one_slice = li.res < (1u << plan.shift[level]) && !__ballot(gi[0] >= li.res);
+            if constexpr (pair_in_flight<D, F, PT>()) {
+                constexpr int M = 1 << (D - 1);
+                constexpr uint32_t entry_bytes = F * sizeof(PT);
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<PT *>(table), 0, (int)(li.size * entry_bytes), 0x00020000);
+                uint32_t idx0[M], idx1[M];
+                float wa[M], wb[M], ea[M][2 * F], eb[M][F];
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    uint32_t h = 0;  // (the pair term -- h and wa / wb -- has twins in add_pair and add_pair_runs)
+                    wa[m] = 1.0f - w[0]; wb[m] = w[0];  // ((t0*t1)*t2)*t3, as the generic loop
+#pragma unroll
+                    for (int d = 1; d < D; ++d) {
+                        const uint32_t bit = ((uint32_t)m >> (d - 1)) & 1u;
+                        h ^= (gi[d] + bit) * primes[d];
+                        const float td = bit ? w[d] : 1.0f - w[d];
+                        wa[m] *= td; wb[m] *= td;
+                    }
+                    idx0[m] = (gi[0] ^ h) & maskv; idx1[m] = ((gi[0] + 1u) ^ h) & maskv;
+                    // A: the aligned pair that holds idx0 (and, for even x, idx1 = idx0 ^ 1).  B: idx1 for odd x; for even x an offset past the
+                    // level's bytes, which the buffer range check answers with zeros without a memory access.
+                    const uint32_t off_a = (idx0[m] & ~1u) * entry_bytes, off_b = x_even ? 0x80000000u : idx1[m] * entry_bytes;
+                    if constexpr (F == 1) {
+                        const auto a = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off_a, 0, 0);
+                        ea[m][0] = __uint_as_float(a[0]); ea[m][F] = __uint_as_float(a[1]);
+                        eb[m][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)off_b, 0, 0));
+                    } else {
+                        const auto a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off_a, 0, 0);
+                        const auto b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off_b, 0, 0);
+                        ea[m][0] = __uint_as_float(a[0]); ea[m][1] = __uint_as_float(a[1]); ea[m][2] = __uint_as_float(a[2]); ea[m][3] = __uint_as_float(a[3]);
+                        eb[m][0] = __uint_as_float(b[0]); eb[m][1] = __uint_as_float(b[1]);
+                    }
+                }
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    const bool hi = (idx0[m] & 1u) != 0u;
+#pragma unroll
+                    for (int f = 0; f < F; ++f) {
+                        const float lo = ea[m][f], up = ea[m][F + f];
+                        acc[f] = pair_term(F == 1 || m + 1 < M, wa[m], hi ? up : lo, acc[f]);
+                    }
+#pragma unroll
+                    for (int f = 0; f < F; ++f) {
+                        const float lo = ea[m][f], up = ea[m][F + f], b = eb[m][f];
+                        const float sibling = hi ? lo : up;
+                        acc[f] = pair_term(F == 1 || m + 1 < M, wb[m], x_even ? sibling : b, acc[f]);
+                    }
+                    if (masks) {
+                        set_row<Q>(mask, slice_of(plan, level, idx0[m]));
+                        if (!x_pair_one_slice) set_row<Q>(mask, slice_of(plan, level, idx1[m]));  // (level-uniform)
+                    }
+                }
+            } else {
 #pragma unroll
             for (uint32_t m = 0; m < (1u << (D - 1)); ++m) {
                 uint32_t h = 0;  // (the pair term -- h and, below, wa / wb -- has twins in add_pair and add_pair_runs)
@@ -538,6 +616,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const emer_grid_desc 
                     set_row<Q>(mask, slice_of(plan, level, idx0));
                     if (!x_pair_one_slice) set_row<Q>(mask, slice_of(plan, level, idx1));  // (level-uniform)
                 }
+            }
             }
         }
         }

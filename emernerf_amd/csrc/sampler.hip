@@ -33,7 +33,7 @@ __device__ __forceinline__ float stot_inv_map(int type, float s) {
     if (type == EMER_STOT_UNIFORM_LINDISP) return s < 0.5f ? s * 400.0f : (1.0f / (2.0f - 2.0f * s)) * 200.0f;
     if (type == EMER_STOT_LINDISP) return 1.0f / s;
     if (type == EMER_STOT_SQRT) return s * s;
-    if (type == EMER_STOT_LOG) return expf(s);  // (libm-dependent last bit: compared by tolerance, not bit-exact)
+    if (type == EMER_STOT_LOG) return expf(s);  // (library expf: held within LOG_ULP_DEVICE of exp of the fp32 argument, tests/test_sample_exact_gpu.py)
     if (type == EMER_STOT_UNIFORM_LINDISP_0) return s < 0.5f ? 2.0f * s : 1.0f / (2.0f - 2.0f * s);
     return s;
 }
@@ -165,7 +165,8 @@ extern "C" int emer_importance_sample(const float *vals, const float *cdfs, int6
     EMER_REQUIRE(!t_ends || t_out, "importance_sample: t_ends needs t_out (the interval starts)");
     EMER_REQUIRE(stot_type >= 0 && stot_type <= 5, "importance_sample: unknown stot_type %d", stot_type);
     const float s_min = stot_fwd_map(stot_type, t_min), s_max = stot_fwd_map(stot_type, t_max);
-    const size_t lds = (size_t)kRaysPerBlock * 2 * m * sizeof(float);
+    const size_t lds = (size_t)kRaysPerBlock * 2 * m * sizeof(float);  // above 48 KiB from m = 1537, 128 KiB at m = 4096
+    if (int rc = reserve_lds(reinterpret_cast<const void *>(importance_sample_kernel), lds, "importance_sample")) return rc;
     hipLaunchKernelGGL(importance_sample_kernel, dim3((uint32_t)ceil_div(R, kRaysPerBlock)), dim3(256), lds, as_stream(stream),
                        vals, cdfs, R, m, n, jitter, s_out, t_out, t_ends, s_min, s_max, stot_type);
     return check_launch("importance_sample");

@@ -266,9 +266,13 @@ def test_importance_sample_bit_exact(hip_lib, oracle, R, m, n, stratified):
     assert np.array_equal(s.cpu().numpy().view(np.uint32), ref.view(np.uint32)), "sample offsets must be bit-exact"
     assert np.array_equal(t.cpu().numpy().view(np.uint32), ref_t.view(np.uint32)), "s->t must be bit-exact"
     assert (np.diff(ref, axis=-1) >= 0).all()
-    for typ in ("uniform", "lindisp", "uniform_lindisp"):
+    from tests import _sample_probe as SP
+    for typ in ("uniform", "lindisp", "uniform_lindisp", "sqrt", "log", "uniform_lindisp_0"):
         a = ops.stot(s, 0.5, 300.0, typ).cpu().numpy()
-        assert np.array_equal(a.view(np.uint32), oracle.stot(ref, 0.5, 300.0, typ).view(np.uint32))
+        if typ == "log":     # the device library's expf: tests/_sample_probe.LOG_ULP_DEVICE
+            SP.check_log(f"stot log R={R} m={m} n={n}", a, SP.stot_arg("log", ref, 0.5, 300.0), SP.LOG_ULP_DEVICE)
+        else:
+            assert np.array_equal(a.view(np.uint32), oracle.stot(ref, 0.5, 300.0, typ).view(np.uint32)), typ
 
 
 def test_importance_sample_end_clamp_bit_exact(hip_lib, oracle):

@@ -144,6 +144,11 @@ SIGNATURES = {
     "emer_feature_colours": [_P, c_int32, c_int64, c_int32, _P],
     "emer_blend_over": [_P, c_int32, c_int64, _P],
     "emer_flow_colours": [_P, c_int32, c_int64, _P, c_float, c_int32, _P],
+    "emer_voxel_mark": [_P, c_int32, c_int64, _P],
+    "emer_mean_threshold_bits": [_P, c_int32, c_int64, c_float, _P, _P],
+    "emer_bits_offsets": [_P, c_int64, _P, _P],
+    "emer_bits_emit_voxels": [_P, _P, c_int64, _P, _P, _P, _P, _P, _P],
+    "emer_bits_emit_rows": [_P, c_int64, _P, c_int64, _P, c_int32, _P, _P],
     "emer_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_int32, _P],
 }
 
@@ -158,6 +163,7 @@ INT64_FUNCTIONS = {
     "emer_importance_sample_points_capacity": [],
     "emer_ssim_workspace": [c_int32, c_int32],
     "emer_sq_err_sums_workspace": [c_int64, c_int32],
+    "emer_bits_offsets_size": [c_int64],
 }
 
 ALLOW_MISSING_SYMBOLS = False  # never set by the product path

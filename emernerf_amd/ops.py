@@ -1490,3 +1490,142 @@ def flow_colours_multi(flows, max_radius: Optional[float] = 1.0, background: str
 def flow_colours(flow: Tensor, max_radius: Optional[float] = 1.0, background: str = "bright") -> Tensor:
     """``scene_flow_to_rgb(flow, flow_max_radius=max_radius, background=background)`` on the device (see ``flow_colours_multi``)."""
     return flow_colours_multi([flow], max_radius, background)[0]
+
+
+# ------------------------------------------------------------------------------------ voxel lift (bit masks)
+VOXEL_JOBS_MAX = 4
+MEAN_ARRAYS_MAX = 8
+BITS_ROW_COLS_MAX = 4
+
+
+class _VoxelMarkJob(ctypes.Structure):
+    """emer_voxel_mark_job of include/emernerf_hip.h."""
+    _fields_ = [("origins", ctypes.c_void_p), ("viewdirs", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("bits", ctypes.c_void_p),
+                ("max_depth", ctypes.c_float), ("aabb_min", ctypes.c_float * 3), ("voxel_size", ctypes.c_float * 3),
+                ("res", ctypes.c_int32 * 3)]
+
+
+def bit_words(n_bits: int) -> int:
+    """Words of a mask of ``n_bits`` bits (bit n: word n // 32, position n % 32)."""
+    return (int(n_bits) + 31) // 32
+
+
+def _bits(bits: Tensor, n_bits: int, what: str) -> Tensor:
+    if bits.dtype != torch.int32 or bits.dim() != 1 or not bits.is_contiguous() or bits.numel() != bit_words(n_bits):
+        raise _lib.EmerError(f"{what}: the mask of {n_bits} bits is a contiguous int32 tensor of {bit_words(n_bits)} words, got "
+                             f"{bits.dtype} {tuple(bits.shape)}")
+    return bits
+
+
+def _triple(v, kind, what: str):
+    """Three host numbers (a sequence or a CPU / device tensor of 3 elements) -> a tuple of python ints or floats."""
+    vals = v.detach().reshape(-1).tolist() if isinstance(v, Tensor) else list(v)
+    if len(vals) != 3:
+        raise _lib.EmerError(f"{what}: expected 3 values, got {len(vals)}")
+    return tuple(kind(x) for x in vals)
+
+
+def _voxel_count(res, what: str) -> int:
+    if any(r < 1 or r >= 1 << 24 for r in res) or res[0] * res[1] * res[2] > 2 ** 31 - 1:
+        raise _lib.EmerError(f"{what}: resolution {res}: every axis in 1 .. 2^24 - 1 and at most 2^31 - 1 voxels")
+    return res[0] * res[1] * res[2]
+
+
+def voxel_mark(jobs) -> None:
+    """Mark the voxels that hold the ray end points ``origins + viewdirs * depth`` (emer_voxel_mark): ``jobs`` is a list of
+    ``(origins [..., 3], viewdirs [..., 3], depth [...], max_depth, aabb_min (3), voxel_size (3), res (3), bits)`` that share the
+    ray count and run as ONE launch (the static and the dynamic grid of an image).  ``bits`` is the grid's int32 mask of
+    ``bit_words(prod(res))`` words and is updated in place (clear it with ``zero_()``); ``max_depth`` drops the rays with
+    ``depth >= max_depth`` (``inf``: none).  The arithmetic is the reference's fp32 chain (visualization_tools.py:546-567,
+    datasets/utils.py:85-88), the conversion truncates toward zero."""
+    if not 1 <= len(jobs) <= VOXEL_JOBS_MAX:
+        raise _lib.EmerError(f"voxel_mark: 1..{VOXEL_JOBS_MAX} jobs, got {len(jobs)}")
+    arr, keep = (_VoxelMarkJob * len(jobs))(), []
+    n_rays = None
+    for i, (origins, viewdirs, depth, max_depth, aabb_min, voxel_size, res, bits) in enumerate(jobs):
+        _check_cuda(origins, viewdirs, depth, bits)
+        o, d = _rows(origins, 3, "voxel_mark: origins"), _rows(viewdirs, 3, "voxel_mark: viewdirs")
+        if n_rays is None:
+            n_rays = o.shape[0]
+        if o.shape[0] != n_rays or d.shape[0] != n_rays:
+            raise _lib.EmerError("voxel_mark: origins, viewdirs and the jobs of one launch share the ray count")
+        t = _per_row(depth, n_rays, "voxel_mark: depth")
+        res3 = _triple(res, int, "voxel_mark: res")
+        b = _bits(bits, _voxel_count(res3, "voxel_mark"), "voxel_mark")
+        if not (o.device == d.device == t.device == b.device):
+            raise _lib.EmerError("voxel_mark: the rays and the mask of a job live on one device")
+        keep.append((o, d, t, b))
+        arr[i] = _VoxelMarkJob(o.data_ptr(), d.data_ptr(), t.data_ptr(), b.data_ptr(), float(max_depth),
+                               (ctypes.c_float * 3)(*_triple(aabb_min, float, "voxel_mark: aabb_min")),
+                               (ctypes.c_float * 3)(*_triple(voxel_size, float, "voxel_mark: voxel_size")), (ctypes.c_int32 * 3)(*res3))
+    ref = keep[0][3]
+    with torch.cuda.device(ref.device):
+        _lib.call("emer_voxel_mark", arr, len(jobs), n_rays, _stream(ref))
+
+
+def _bit_offsets(bits: Tensor, n_bits: int):
+    """(offsets, total): the per-workgroup exclusive offsets of a mask's set bits and their number -- the ONE host read of a
+    compaction."""
+    with torch.cuda.device(bits.device):
+        offsets = torch.empty(int(_lib.load().emer_bits_offsets_size(n_bits)), dtype=torch.int64, device=bits.device)
+        _lib.call("emer_bits_offsets", _ptr(bits), n_bits, _ptr(offsets), _stream(bits))
+    return offsets, int(offsets[-1].item())
+
+
+def bits_nonzero_voxels(bits: Tensor, res, aabb_min, voxel_size, want_indices: bool = False):
+    """The set bits of a voxel mask in ascending order as world corners ``aabb_min + float(i) * voxel_size`` ([M, 3] fp32; with
+    ``want_indices`` also the [M, 3] int32 voxel indices): ``voxel_coords_to_world_coords(torch.nonzero(grid))`` of the
+    reference.  One host synchronisation (the count); an empty mask gives [0, 3] outputs."""
+    _check_cuda(bits)
+    res3 = _triple(res, int, "bits_nonzero_voxels: res")
+    n_bits = _voxel_count(res3, "bits_nonzero_voxels")
+    _bits(bits, n_bits, "bits_nonzero_voxels")
+    amin, vs = _triple(aabb_min, float, "bits_nonzero_voxels: aabb_min"), _triple(voxel_size, float, "bits_nonzero_voxels: voxel_size")
+    offsets, total = _bit_offsets(bits, n_bits)
+    coords = torch.empty(total, 3, dtype=torch.float32, device=bits.device)
+    indices = torch.empty(total, 3, dtype=torch.int32, device=bits.device) if want_indices else None
+    with torch.cuda.device(bits.device):
+        _lib.call("emer_bits_emit_voxels", _ptr(bits), _ptr(offsets), total, (ctypes.c_int32 * 3)(*res3), (ctypes.c_float * 3)(*amin),
+                  (ctypes.c_float * 3)(*vs), _ptr(coords), _ptr(indices), _stream(bits))
+    return (coords, indices) if want_indices else coords
+
+
+def bits_select_rows(bits: Tensor, src: Tensor) -> Tensor:
+    """``src[selector]`` for a [N, C] fp32 ``src`` (C <= 4; a [N] tensor counts as C = 1 and gives [M]) and the selector held as a
+    mask of N bits: the rows whose bit is set, in ascending order.  One host synchronisation (the count)."""
+    _check_cuda(bits, src)
+    if src.dim() not in (1, 2) or src.dtype != torch.float32 or (src.dim() == 2 and not 1 <= src.shape[1] <= BITS_ROW_COLS_MAX):
+        raise _lib.EmerError(f"bits_select_rows: src is fp32 [N] or [N, 1..{BITS_ROW_COLS_MAX}], got {src.dtype} {tuple(src.shape)}")
+    if src.device != bits.device:
+        raise _lib.EmerError("bits_select_rows: the mask and the rows live on one device")
+    n, cols = src.shape[0], (src.shape[1] if src.dim() == 2 else 1)
+    _bits(bits, n, "bits_select_rows")
+    if n == 0:
+        return src.detach().clone()
+    s = _f32c(src)
+    offsets, total = _bit_offsets(bits, n)
+    out = torch.empty((total, cols) if src.dim() == 2 else (total,), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.call("emer_bits_emit_rows", _ptr(bits), n, _ptr(offsets), total, _ptr(s), cols, _ptr(out), _stream(s))
+    return out
+
+
+def mean_threshold_bits(densities, thr: float) -> Tensor:
+    """The selector ``mean(stack(densities), 0) > thr`` of K fp32 arrays of one length N as a mask of N bits (int32 words):
+    ``((d0 + d1) + ...) / K > thr`` with a sequential fp32 sum and one division; K = 1 is ``d0 > thr``.  NaN selects nothing."""
+    if isinstance(densities, Tensor):
+        densities = [densities]
+    if not 1 <= len(densities) <= MEAN_ARRAYS_MAX:
+        raise _lib.EmerError(f"mean_threshold_bits: 1..{MEAN_ARRAYS_MAX} arrays, got {len(densities)}")
+    _check_cuda(*densities)
+    n = densities[0].numel()
+    ds = []
+    for d in densities:
+        if d.numel() != n or d.dtype != torch.float32 or d.device != densities[0].device:
+            raise _lib.EmerError("mean_threshold_bits: the arrays are fp32, of one length and on one device")
+        ds.append(_f32c(d).reshape(n))
+    bits = torch.empty(bit_words(n), dtype=torch.int32, device=ds[0].device)
+    ptrs = (ctypes.c_void_p * len(ds))(*[d.data_ptr() for d in ds])
+    with torch.cuda.device(ds[0].device):
+        _lib.call("emer_mean_threshold_bits", ptrs, len(ds), n, float(thr), _ptr(bits), _stream(ds[0]))
+    return bits

@@ -902,6 +902,50 @@ int emer_flow_colours(const emer_flow_colour_job *jobs, int32_t n_jobs, int64_t 
                       int32_t dark_background, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Voxel lift of the feature field (utils/visualization_tools.py:456-701, csrc/voxels.hip): ray end points to occupied voxels,
+ * density selectors and their gathers, all over BIT MASKS -- bit n lives in word n / 32 at position n % 32 of a uint32 buffer of
+ * ceil(n_bits / 32) words.  A voxel grid of resolution res[3] has the linear index (ix * res[1] + iy) * res[2] + iz (the
+ * row-major order of torch.nonzero) and at most EMER_VOXELS_MAX voxels.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMER_VOXEL_JOBS_MAX 4
+#define EMER_VOXELS_MAX 2147483647ll
+#define EMER_MEAN_ARRAYS_MAX 8
+#define EMER_BITS_BLOCK_BITS 8192      /* bits of a mask that one compaction workgroup owns */
+#define EMER_BITS_ROW_COLS_MAX 4
+/* Mark the voxels that hold a ray's end point.  Per ray, in fp32, every operation rounded on its own and in this order:
+ * keep if depth < max_depth (+inf: no filter); p = origin + viewdir * depth; v = (p - aabb_min) / voxel_size; i = trunc(v)
+ * toward zero, as Tensor.long() (so -1 < v < 0 lands in voxel 0, as in the reference); keep if 0 <= i < res on every axis.  The
+ * range test is made on v, a row with a non-finite coordinate is dropped.  voxel_size is the caller's
+ * (aabb_max - aabb_min) / res in fp32 (datasets/utils.py:85).  origins / viewdirs [n_rays][3], depth [n_rays] fp32; bits: the
+ * grid's mask, which the caller cleared (marking accumulates over calls).  Bits are set with atomic ORs: the mask does not
+ * depend on the order.  The jobs (the static and the dynamic grid of one image) share n_rays and ONE launch. */
+typedef struct emer_voxel_mark_job {
+    const float *origins, *viewdirs, *depth; uint32_t *bits;
+    float max_depth, aabb_min[3], voxel_size[3]; int32_t res[3];
+} emer_voxel_mark_job;
+int emer_voxel_mark(const emer_voxel_mark_job *jobs, int32_t n_jobs, int64_t n_rays, void *stream);
+/* bit i = (((d[0][i] + d[1][i]) + ...) + d[n_arrays - 1][i]) / n_arrays > threshold for i < n: a sequential fp32 sum and one
+ * division (n_arrays = 1: d[0][i] > threshold); NaN selects nothing.  densities: HOST array of n_arrays device pointers to
+ * [n] fp32.  Every word of the mask is written, the bits past n in the last word are 0. */
+int emer_mean_threshold_bits(const float *const *densities, int32_t n_arrays, int64_t n, float threshold, uint32_t *bits,
+                             void *stream);
+/* Ordered compaction of a mask of n_bits bits.  emer_bits_offsets fills offsets [emer_bits_offsets_size(n_bits)] (int64, device):
+ * offsets[b] = the number of set bits before workgroup b's EMER_BITS_BLOCK_BITS bits, the last element = the total, which the
+ * caller reads back (its one synchronisation) to allocate the output.  The emit entries then write one row per set bit in
+ * ascending bit order (total == 0: no launch); the mask must not change in between.  Bits past n_bits are ignored.  No atomics:
+ * the output is identical from run to run.
+ *   voxels: bit -> (ix, iy, iz) -> coords[m] = aabb_min + float(i) * voxel_size, a product then a sum
+ *           (voxel_coords_to_world_coords, datasets/utils.py:47-52), [total][3] fp32; indices [total][3] int32 or NULL.
+ *           res, aabb_min, voxel_size: HOST arrays of 3.
+ *   rows:   bit n -> out[m][:] = src[n][:], src [n_bits][n_cols] fp32, 1 <= n_cols <= EMER_BITS_ROW_COLS_MAX (points[selector]). */
+int64_t emer_bits_offsets_size(int64_t n_bits);
+int emer_bits_offsets(const uint32_t *bits, int64_t n_bits, int64_t *offsets, void *stream);
+int emer_bits_emit_voxels(const uint32_t *bits, const int64_t *offsets, int64_t total, const int32_t *res, const float *aabb_min,
+                          const float *voxel_size, float *coords, int32_t *indices, void *stream);
+int emer_bits_emit_rows(const uint32_t *bits, int64_t n_bits, const int64_t *offsets, int64_t total, const float *src,
+                        int32_t n_cols, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer (torch.optim.Adam as configured in builders.py:50-60,114-120: eps 1e-15,
  * betas (0.9, 0.99), weight_decay as L2) over one flat fp32 buffer; grad_scale multiplies the
  * gradient first (1/world_size after the RCCL all-reduce; GradScaler quirk).

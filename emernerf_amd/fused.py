@@ -12,11 +12,13 @@ once by the forward and read once as relu' masks / wgrad operands.
 
 Two implementations sit behind each Function: the register-resident kernels of csrc/mlp_fused.hip (hidden width 64,
 the shapes every shipped config uses: ``emer_neck_*``, ``emer_rgb_head_*``) and the generic LDS-staged
-``emer_mlp_chain`` for any other width.  Both are HIP; there is no torch fallback.
+``emer_mlp_chain`` for any other width that fits its row buffer (512 columns) and LDS (160 KiB at four waves); heads beyond that
+(``*_supported`` below) run layer by layer on ``emer_linear_*``.  All are HIP; there is no torch fallback.
 """
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 import ctypes
 from ctypes import c_int32, c_int64, c_void_p
@@ -145,6 +147,11 @@ def run_chain(segs, layers, buf_cols: int, n_rows: int, ref: Tensor) -> None:
     for i, s in enumerate(segs):
         d.segs[i] = s
     for i, l in enumerate(layers):
+        # the kernel finishes one group of 64 output columns (GEMM over the whole K, then the epilogue's writes) before the next:
+        # only the LAST group of a layer may write over the layer's own input
+        if l.N > 64 and l.in_col < l.out_col + 64 * ((l.N - 1) // 64) and l.out_col < l.in_col + l.K:
+            raise ValueError(f"chain layer {i}: output columns {l.out_col}..{l.out_col + l.N} written before the layer's last column "
+                             f"group overlap its input {l.in_col}..{l.in_col + l.K}")
         d.layers[i] = l
     d.n_segs, d.n_layers, d.buf_cols = len(segs), len(layers), buf_cols
     with torch.cuda.device(ref.device):
@@ -268,6 +275,86 @@ def _c(t: Tensor) -> Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+# ------------------------------------------------------------------------- row-buffer layouts of the chain heads
+def _ru(x: int, m: int) -> int:
+    return -(-x // m) * m
+
+
+def chain_fits(buf_cols: int, kn) -> bool:
+    """emer_mlp_chain's launch conditions for a descriptor with ``buf_cols`` row-buffer columns and layers kn = [(K, N), ...]:
+    at most 512 columns, and the zero-padded weights plus the 16-row buffers of the MINIMUM four waves inside 160 KiB of LDS
+    (chain_lds_plan / emer_mlp_chain of csrc/mlp.hip)."""
+    w = sum(_ru(N, 16) * (_ru(K, 8) + 2) + _ru(N, 16) for K, N in kn)
+    P = _ru(buf_cols + 8, 4) + 2
+    return 4 <= buf_cols <= 512 and (_ru(w, 4) + 4 * 16 * P) * 4 <= 160 * 1024
+
+
+def _skip_cols(H: int, K0: int, C: int):
+    """Forward columns of the 3-layer skip heads: [A1 | x] from column 0 exactly like torch.cat([x_hidden, input]) of mlp.py:42,
+    then A2, then the output.  A layer of at most 64 outputs is ONE column group of the kernel: every input column has been
+    consumed by the MFMAs before its epilogue writes, so A2 may overwrite A1 in place (a smaller row buffer buys more waves per
+    CU).  A wider layer runs group after group over the whole K, and group 1 would read an A1 whose first 64 columns already
+    hold A2: it gets columns of its own.  Returns (c_x, c_a2, c_o, buf_cols)."""
+    c_x = _r4(H)
+    c_e = c_x + _r4(K0)
+    c_a2 = 0 if c_x <= 64 else c_e
+    c_o = c_e if c_a2 == 0 else c_e + c_x
+    return c_x, c_a2, c_o, c_o + _r4(C)
+
+
+def base_mlp_chain_shapes(K0: int, H: int, NG: int):
+    """[(buf_cols, [(K, N) per layer])] of base_mlp's forward and backward chains."""
+    return [(_r4(K0) + _r4(H) + NG, [(K0, H), (H, NG)]), (_r4(NG) + _r4(H) + K0, [(NG, H), (H, K0)])]
+
+
+def density_mlp_chain_shapes(K0: int, H: int):
+    return [(_r4(K0) + _ru(H, 8) + 4, [(K0, H), (H, 1)]), (4 + _r4(H) + K0, [(1, H), (H, K0)])]
+
+
+def rgb_head_chain_shapes(H: int, Kh: int, NG: int, C: int):
+    K0 = Kh + NG
+    return [(_skip_cols(H, K0, C)[3], [(K0, H), (H + K0, H), (H, C)]),
+            (_r4(C) + 2 * H + K0, [(C, H), (H, H), (H, K0), (H, Kh), (H, NG)])]
+
+
+def skip_mlp3_chain_shapes(H: int, K0: int, C: int):
+    return [(_skip_cols(H, K0, C)[3], [(K0, H), (H + K0, H), (H, C)]),
+            (_r4(C) + 2 * H + _r4(K0), [(C, H), (H, H), (H, K0), (H, K0)])]
+
+
+def _all_fit(shapes) -> bool:
+    return all(chain_fits(b, kn) for b, kn in shapes)
+
+
+@functools.lru_cache(maxsize=None)
+def base_mlp_supported(K0: int, H: int, NG: int) -> bool:
+    """The forward and the backward chain of base_mlp fit the chain kernel (otherwise base_mlp runs layer by layer)."""
+    return _all_fit(base_mlp_chain_shapes(K0, H, NG))
+
+
+@functools.lru_cache(maxsize=None)
+def density_mlp_supported(K0: int, H: int) -> bool:
+    return _all_fit(density_mlp_chain_shapes(K0, H))
+
+
+@functools.lru_cache(maxsize=None)
+def rgb_head_supported(H: int, Kh: int, NG: int, C: int) -> bool:
+    return H % 4 == 0 and _all_fit(rgb_head_chain_shapes(H, Kh, NG, C))
+
+
+@functools.lru_cache(maxsize=None)
+def skip_mlp3_supported(H: int, K0: int, C: int) -> bool:
+    return H % 4 == 0 and _all_fit(skip_mlp3_chain_shapes(H, K0, C))
+
+
+def _skip3_layers(x: Tensor, w0, b0, w1, b1, w2, b2, final_act: int) -> Tensor:
+    """The 3-layer skip MLP layer by layer on emer_linear_* (ops.linear): heads too wide for one chain launch."""
+    from . import ops
+    h = ops.linear(x, w0, b0, "relu")
+    h = ops.linear(torch.cat([h, x], dim=-1), w1, b1, "relu")
+    return ops.linear(h, w2, b2, "sigmoid" if final_act == ACT_SIGMOID else None)
+
+
 # ------------------------------------------------------------------------------------------ base MLP
 class _BaseMLPFn(torch.autograd.Function):
     @staticmethod
@@ -318,6 +405,10 @@ class _BaseMLPFn(torch.autograd.Function):
 
 def base_mlp(enc_lm: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor) -> Tuple[Tensor, Tensor]:
     """(feats [N, NG], density [N]) from the level-major grid encoding [L, N, F]."""
+    L, _, F = enc_lm.shape
+    if not base_mlp_supported(L * F, w0.shape[0], w1.shape[0]):
+        from . import ops   # too wide for one chain launch: layer by layer on emer_linear_*
+        return ops.linear_with_density(ops.linear(ops.lm_to_rm(enc_lm), w0, b0, "relu"), w1, b1)
     return _BaseMLPFn.apply(*_ng(enc_lm, w0, b0, w1, b1))
 
 
@@ -490,7 +581,10 @@ class _DensityMLPFn(torch.autograd.Function):
         h = torch.empty((N, H), device=dev, dtype=torch.float32) if need_grad else None
         dens = torch.empty((N, 1), device=dev, dtype=torch.float32)
         c_h = _r4(K0)
-        c_o = c_h + _r4(H)
+        # the output column lies past the K % 8 padding of layer 1: the kernel reads round_up(H, 8) columns from c_h (the tail
+        # meets zero weights) and keeps the row buffer from tile to tile, so a density that overflowed to inf in a wave's
+        # previous tile must not sit in that tail (inf * 0 = NaN on the same row of the wave's next tile)
+        c_o = c_h + _ru(H, 8)
         run_chain([seg_lm(enc, 0)],
                   [layer(W0, B0, 0, c_h, ACT_RELU, store=h), layer(W1, B1, c_h, c_o, ACT_TRUNC_EXP, store=dens)],
                   c_o + 4, N, enc)
@@ -548,6 +642,10 @@ class _DensityMLPFn(torch.autograd.Function):
 
 def density_mlp(enc_lm: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor) -> Tensor:
     """trunc_exp(Linear(ReLU(Linear(enc))) - 1) -> [N]."""
+    L, N, F = enc_lm.shape
+    if not neck_supported(L, F, w0.shape[0], 1) and not density_mlp_supported(L * F, w0.shape[0]):
+        from . import ops   # too wide for one chain launch: layer by layer on emer_linear_*
+        return ops.linear(ops.linear(ops.lm_to_rm(enc_lm), w0, b0, "relu"), w1, b1, "trunc_exp").view(N)
     return _DensityMLPFn.apply(*_ng(enc_lm, w0, b0, w1, b1))
 
 
@@ -597,15 +695,12 @@ class _RgbHeadFn(torch.autograd.Function):
                           _p(a1), _p(a2), _p(out), _stream(g))
             ctx.save_for_backward(hr, g, W0, W1, W2, a1, a2, out, rb if ctx.recompute else None)
             return out
-        c_x = _r4(H)               # [A1 | hray | geo] laid out exactly like torch.cat([x, input]) of mlp.py:42
-        # A2 overwrites A1 in place: a <= 64-wide layer is one column group, so every input column has been
-        # consumed by the MFMAs before the epilogue writes.  The smaller row buffer buys more waves per CU.
-        c_o = c_x + _r4(K0)
+        c_x, c_a2, c_o, cols = _skip_cols(H, K0, C)   # [A1 | hray | geo], A2 in place over A1 when H <= 64 (see _skip_cols)
         run_chain([seg(hr, c_x, Kh, row_div=S), seg(g, c_x + Kh, NG, ld=g.stride(0))],
                   [layer(W0, B0, c_x, 0, ACT_RELU, store=a1),
-                   layer(W1, B1, 0, 0, ACT_RELU, store=a2),
-                   layer(W2, B2, 0, c_o, ACT_SIGMOID, store=out)],
-                  c_o + 4, N, g)
+                   layer(W1, B1, 0, c_a2, ACT_RELU, store=a2),
+                   layer(W2, B2, c_a2, c_o, ACT_SIGMOID, store=out)],
+                  cols, N, g)
         ctx.save_for_backward(hr, g, W0, W1, W2, a1, a2, out, None)
         return out
 
@@ -710,6 +805,9 @@ class _RgbHeadFn(torch.autograd.Function):
 
 def rgb_head(hray: Tensor, geo: Tensor, samples_per_ray: int, w0, b0, w1, b1, w2, b2) -> Tensor:
     """sigmoid(MLP3-skip1([hray[ray] | geo])) -> [N, 3]; hray [R, Kh] per ray, geo [N, NG] per sample."""
+    if not rgb_head_supported(w0.shape[0], hray.shape[1], geo.shape[1], w2.shape[0]):
+        # too wide for one chain launch: the concatenated rows, layer by layer on emer_linear_*
+        return _skip3_layers(torch.cat([hray.repeat_interleave(samples_per_ray, dim=0), geo], dim=-1), w0, b0, w1, b1, w2, b2, ACT_SIGMOID)
     pre = _RIDERS.pop(geo.data_ptr(), None)
     if pre is not None:  # the same query, tensor for tensor, that rode along in the neck's launch?
         same = (pre.S == samples_per_ray and pre.hray.data_ptr() == hray.data_ptr() and pre.hray.shape == hray.shape
@@ -866,13 +964,12 @@ class _SkipMLP3Fn(torch.autograd.Function):
                 _lib.call("emer_ray_head_fwd", _p(rb), 2 * H, N, _p(W1), W1.stride(0), _p(W2), _p(B2), C, final_act, _p(a1), _p(a2), _p(out),
                           _stream(X))
         else:
-            c_x = H                     # [A1 | x] laid out exactly like torch.cat([x_hidden, input]) of mlp.py:42
-            c_o = c_x + _r4(K0)
+            c_x, c_a2, c_o, cols = _skip_cols(H, K0, C)   # [A1 | x], A2 in place over A1 when H <= 64 (see _skip_cols)
             run_chain([seg(X, c_x, K0)],
                       [layer(W0, B0, c_x, 0, ACT_RELU, store=a1),
-                       layer(W1, B1, 0, 0, ACT_RELU, store=a2),     # A2 overwrites A1 in place (one column group)
-                       layer(W2, B2, 0, c_o, final_act, store=out)],
-                      c_o + _r4(C), N, X)
+                       layer(W1, B1, 0, c_a2, ACT_RELU, store=a2),
+                       layer(W2, B2, c_a2, c_o, final_act, store=out)],
+                      cols, N, X)
         ctx.save_for_backward(X, W0, W1, W2, a1, a2, out)
         ctx.final_act = final_act
         ctx.sinks = tuple(_sink(p) for p in (w0, b0, w1, b1, w2, b2))
@@ -936,6 +1033,8 @@ class _SkipMLP3Fn(torch.autograd.Function):
 def skip_mlp3(x: Tensor, w0, b0, w1, b1, w2, b2, final_act: int = ACT_SIGMOID) -> Tensor:
     """final_act(MLP3-skip1(x)) for x [rows, K0]; final_act ACT_SIGMOID or ACT_NONE."""
     assert final_act in (ACT_SIGMOID, ACT_NONE)
+    if not skip_mlp3_supported(w0.shape[0], x.shape[1], w2.shape[0]):
+        return _skip3_layers(x, w0, b0, w1, b1, w2, b2, final_act)   # too wide for one chain launch
     front = ray_jobs.front_sky(x, (w0, b0, w1, b1, w2, b2), final_act)
     return _SkipMLP3Fn.apply(*_ng(x, w0, b0, w1, b1, w2, b2, final_act), front)
 
@@ -947,7 +1046,17 @@ def seq_mlp_supported(weights) -> bool:
         return False
     lds = sum((-(-w.shape[0] // 16) * 16) * ((-(-w.shape[1] // 8) * 8) + 2) * 4 for w in weights)
     cols = _r4(weights[0].shape[1]) + sum(_r4(w.shape[0]) for w in weights)
-    return lds <= 96 * 1024 and cols <= 500 and all(w.shape[0] <= 256 for w in weights)
+    if not (lds <= 96 * 1024 and cols <= 500 and all(w.shape[0] <= 256 for w in weights)):
+        return False
+    return _all_fit(seq_mlp_chain_shapes([w.shape[1] for w in weights] + [weights[-1].shape[0]]))
+
+
+def seq_mlp_chain_shapes(dims):
+    """[(buf_cols, [(K, N) per layer])] of seq_mlp's forward and backward (with dx) chains for Linear widths dims[0] -> ... -> dims[-1]."""
+    n = len(dims) - 1
+    fwd = (_r4(dims[0]) + sum(_r4(d) for d in dims[1:]), [(dims[i], dims[i + 1]) for i in range(n)])
+    bwd = (sum(_r4(d) for d in dims), [(dims[i + 1], dims[i]) for i in range(n - 1, -1, -1)])
+    return [fwd, bwd]
 
 
 class _SeqMLPFn(torch.autograd.Function):
@@ -1142,6 +1251,12 @@ def seq_mlp(x: Tensor, weights, biases, final_act: int = ACT_NONE) -> Tensor:
     wb = [t for pair in zip(weights, biases) for t in pair]
     if x.shape[-1] % 4 == 0 and rmlp_supported(weights, x.shape[-1], 0):
         return _RMlpFn.apply(*_ng(x, False, final_act, *wb))
+    if not seq_mlp_supported(weights):
+        from . import ops   # too wide (or too deep) for one chain launch: layer by layer on emer_linear_*
+        n = len(weights)
+        for i, (w, b) in enumerate(zip(weights, biases)):
+            x = ops.linear(x, w, b, "relu" if i + 1 < n else ("sigmoid" if final_act == ACT_SIGMOID else None))
+        return x
     return _SeqMLPFn.apply(*_ng(x, final_act, *wb))
 
 

@@ -595,7 +595,8 @@ class RadianceField(nn.Module):
 
     def _query_rgb_fused(self, directions, geo_feats, dynamic_geo_feats, data_dict):
         """Fused rgb head: per-ray [dir-PE | appearance emb] stays per ray, geo stays per sample, the whole
-        3-layer skip MLP + sigmoid is one chain.  Applies when render_rays hands in stride-0 per-ray views."""
+        3-layer skip MLP + sigmoid is one chain (fused.rgb_head; a head too wide for one chain launch -- fused.rgb_head_supported,
+        e.g. 128 or 256 hidden units -- runs layer by layer there).  Applies when render_rays hands in stride-0 per-ray views."""
         head = self.rgb_head
         if not (directions.dim() == 3 and self._per_ray(directions) and len(head.layers) == 3
                 and list(head.skip_connections) == [1] and head.hidden_dims % 4 == 0):

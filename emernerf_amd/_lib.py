@@ -144,6 +144,7 @@ SIGNATURES = {
     "emer_feature_colours": [_P, c_int32, c_int64, c_int32, _P],
     "emer_blend_over": [_P, c_int32, c_int64, _P],
     "emer_flow_colours": [_P, c_int32, c_int64, _P, c_float, c_int32, _P],
+    "emer_compose_frame": [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P],
     "emer_voxel_mark": [_P, c_int32, c_int64, _P],
     "emer_mean_threshold_bits": [_P, c_int32, c_int64, c_float, _P, _P],
     "emer_bits_offsets": [_P, c_int64, _P, _P],

@@ -1492,6 +1492,106 @@ def flow_colours(flow: Tensor, max_radius: Optional[float] = 1.0, background: st
     return flow_colours_multi([flow], max_radius, background)[0]
 
 
+# ------------------------------------------------------------------------------------ video frames (8-bit, merged)
+FRAME_TILES_MAX = 48     # EMER_FRAME_TILES_MAX
+TILE_KINDS = {"colour3": 0, "grey1": 1, "one_minus_grey1": 2, "depth": 3}   # EMER_TILE_*
+_TURBO8: dict = {}
+
+
+class _FrameTile(ctypes.Structure):
+    """emer_frame_tile of include/emernerf_hip.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("opacity", ctypes.c_void_p), ("kind", ctypes.c_int32), ("row", ctypes.c_int32),
+                ("col", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def turbo_table():
+    """The 256 x 3 turbo colours as a float64 numpy array (no GPU needed): matplotlib's listed ``turbo`` map, kept as data in
+    ``_turbo.py``."""
+    import numpy as np
+    from ._turbo import TURBO
+    return np.array(TURBO, dtype=np.float64)
+
+
+def turbo_table_8bit():
+    """``uint8(255 * clip(table, 0, 1))`` in fp64: what the reference's 8-bit cast makes of a depth colour -- one of 256 fixed
+    byte triples.  [256, 3] uint8 numpy array."""
+    import numpy as np
+    return (255 * np.clip(turbo_table(), 0, 1)).astype(np.uint8)
+
+
+def _turbo8_on(device) -> Tensor:
+    t = _TURBO8.get(device)
+    if t is None:
+        t = _TURBO8[device] = torch.from_numpy(turbo_table_8bit()).to(device)
+    return t
+
+
+def depth_range(lo: Optional[float] = 4.0, hi: Optional[float] = 120.0) -> Tuple[float, float]:
+    """``(min(lo', hi'), |hi' - lo'|)`` of the curved bounds ``lo' = -log(lo + 1e-6)``, ``hi' = -log(hi + 1e-6)`` in fp64 (no GPU
+    needed): the two constants of the depth colouring.  ``None`` is the reference's weighted-percentile rule, which needs a sort
+    of the image: not implemented."""
+    import numpy as np
+    if lo is None or hi is None:
+        raise NotImplementedError("depth colours: lo=None / hi=None (the weighted-percentile bounds, which need a sort) are not implemented; "
+                                  "pass both bounds")
+    with np.errstate(all="ignore"):
+        lo_c, hi_c = -np.log(np.float64(lo) + 1e-6), -np.log(np.float64(hi) + 1e-6)
+    return float(np.minimum(lo_c, hi_c)), float(np.abs(hi_c - lo_c))
+
+
+def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool, lo: Optional[float] = 4.0,
+                  hi: Optional[float] = 120.0) -> Tensor:
+    """One merged 8-bit video frame, uint8 [rows * H, cams * W, 3], from device images (emer_compose_frame: ONE launch per
+    ``FRAME_TILES_MAX`` tiles).  ``tiles`` is a list of ``(kind, row, col, src, opacity | None)``: ``src`` fills the cell
+    (row, col) of the frame; ``kind`` is "colour3" (src [H, W, 3]: ``uint8(255 * clip(x, 0, 1))``), "grey1" (src [H, W] on three
+    channels), "one_minus_grey1" (``1 - src``) or "depth" (src and opacity [H, W]: the reference's ``depth_visualizer`` with
+    the bounds ``lo``, ``hi`` -- ``-log(x + 1e-6)`` scaled to [0, 1] between the curved bounds, times the opacity, as a row of
+    the turbo table).  ``fp64_scale``: the product with 255 in fp64, as in the reference's frames that hold a depth row.  A NaN
+    colour is written as 0.  Sources may be views with a storage offset; anything that is not contiguous fp32 is copied.  Cells
+    that no tile names are zero.  A pixel's bytes depend on its own inputs, the kind and the flag alone."""
+    dmin, dabs = depth_range(lo, hi)
+    H, W, rows, cams = int(H), int(W), int(rows), int(cams)
+    if not tiles:
+        raise ValueError("compose_frame: no tiles")
+    arr, keep, cells = (_FrameTile * len(tiles))(), [], set()
+    for i, (kind, row, col, src, opacity) in enumerate(tiles):
+        if kind not in TILE_KINDS:
+            raise ValueError(f"compose_frame: tile {i}: kind should be one of {tuple(TILE_KINDS)}, not {kind!r}")
+        _check_cuda(src, opacity)
+        want = (H, W, 3) if kind == "colour3" else (H, W)
+        if tuple(src.shape) != want:
+            raise ValueError(f"compose_frame: tile {i} ({kind}): expected {want}, got {tuple(src.shape)}")
+        if kind == "depth" and (opacity is None or tuple(opacity.shape) != want):
+            raise ValueError(f"compose_frame: tile {i}: a depth tile needs an opacity of shape {want}")
+        if not (0 <= row < rows and 0 <= col < cams):
+            raise ValueError(f"compose_frame: tile {i}: cell ({row}, {col}) outside the {rows} x {cams} frame")
+        s, o = _f32c(src), (_f32c(opacity) if kind == "depth" else None)
+        keep.append((s, o))
+        cells.add((int(row), int(col)))
+        arr[i] = _FrameTile(s.data_ptr(), None if o is None else o.data_ptr(), TILE_KINDS[kind], int(row), int(col), 0)
+    ref = keep[0][0]
+    shape = (rows * H, cams * W, 3)
+    out = (torch.empty if len(cells) == rows * cams else torch.zeros)(shape, dtype=torch.uint8, device=ref.device)
+    rng = (ctypes.c_double * 2)(dmin, dabs)
+    with torch.cuda.device(ref.device):
+        table = _turbo8_on(ref.device)
+        for first in range(0, len(tiles), FRAME_TILES_MAX):
+            n = min(FRAME_TILES_MAX, len(tiles) - first)
+            part = ctypes.cast(ctypes.byref(arr, first * ctypes.sizeof(_FrameTile)), ctypes.c_void_p)
+            _lib.call("emer_compose_frame", part, n, H, W, rows, cams, 1 if fp64_scale else 0, ctypes.cast(rng, ctypes.c_void_p), _ptr(table),
+                      _ptr(out), _stream(ref))
+    return out
+
+
+def depth_colours(depth: Tensor, opacity: Tensor, lo: Optional[float] = 4.0, hi: Optional[float] = 120.0) -> Tensor:
+    """The reference's ``depth_visualizer`` cut to 8 bits, uint8 [H, W, 3], of a [H, W] depth and opacity: a one-tile frame
+    (see ``compose_frame``)."""
+    if depth.dim() != 2:
+        raise ValueError(f"depth_colours: expected a [H, W] depth, got {tuple(depth.shape)}")
+    H, W = depth.shape
+    return compose_frame([("depth", 0, 0, depth, opacity)], H, W, 1, 1, False, lo, hi)
+
+
 # ------------------------------------------------------------------------------------ voxel lift (bit masks)
 VOXEL_JOBS_MAX = 4
 MEAN_ARRAYS_MAX = 8

@@ -18,7 +18,14 @@ colour-wheel images and a feature model's DINO lists (``dino_feats``, ``gt_dino_
 ``static_dino_feats``, ``dynamic_dino_feats`` and the two cross blends) are produced from the E-wide feature images by the
 kernels of csrc/colours.hip: at most two launches per image for all feature lists, one for the flows; only [H, W, 3] colours
 join the image's transfer.  ``get_robust_pca`` is the reference's robust PCA colour rule (utils/misc.py:23-47) made
-deterministic.  Out of scope here: video encoding, the turbo depth colouring of ``save_videos``, ``resize_five_views``.
+deterministic.
+
+``save_videos`` / ``save_concatenated_videos`` / ``save_seperate_videos`` (video_utils.py:471-627) turn the lists into the
+8-bit frames the reference logs and writes: ``compose_video_frames`` builds each merged frame -- the keys' rows, the turbo
+depth colouring, the cut to 8 bits -- in ONE launch of csrc/frames.hip, so that with ``render(..., to_host=False)`` only
+3 bytes per frame pixel leave the GPU.  Out of scope here: the video encoding itself (imageio's, or the caller's writer),
+the weighted-percentile depth bounds (``lo`` / ``hi`` of None) and ``resize_five_views`` (groups of five views raise unless
+they are tiled unresized).
 """
 from __future__ import annotations
 
@@ -82,12 +89,12 @@ def _unpack(item, out: Dict[str, list]) -> None:
 def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimator, dataset,
                   proposal_networks: Optional[List[DensityField]] = None, compute_metrics: bool = False,
                   vis_indices: Optional[List[int]] = None, return_decomposition: bool = True, visualize: bool = False,
-                  feature_pca: Optional[dict] = None) -> Dict[str, list]:
+                  feature_pca: Optional[dict] = None, to_host: bool = True) -> Dict[str, list]:
     """video_utils.py:50-106.  ``dataset``: anything with ``__len__`` / ``__getitem__`` returning image-shaped ray dicts
     (``PixelSource`` here; the reference's SplitWrapper there).  Nothing here or in ``render`` depends on the image size: with
     ``PixelSource.update_downscale_factor(1 / k)`` set, the same loop is the reference's low-resolution preview pass
     (train_emernerf.py:290-302) on [floor(H / k), floor(W / k)] images; previews smaller than 7 x 7 fall under ``render``'s
-    SSIM rule.  ``visualize`` / ``feature_pca``: see ``render``."""
+    SSIM rule.  ``visualize`` / ``feature_pca`` / ``to_host``: see ``render``."""
     model.eval()
     for p in proposal_networks or []:
         p.eval()
@@ -99,7 +106,7 @@ def render_pixels(cfg, model: RadianceField, proposal_estimator: PropNetEstimato
                            data_dict=data_dict, cfg=cfg, return_decomposition=return_decomposition)
 
     results = render(dataset, render_func, model=model, compute_metrics=compute_metrics, vis_indices=vis_indices, visualize=visualize,
-                     feature_pca=feature_pca)
+                     feature_pca=feature_pca, to_host=to_host)
     if compute_metrics:
         n = len(dataset) if vis_indices is None else len(vis_indices)
         logger.info(f"Eval over {n} images:")
@@ -214,7 +221,8 @@ def _feature_colour_lists(res: Dict[str, Tensor], data: Dict[str, Tensor], model
 
 
 def render(dataset, render_func: Callable, model: Optional[RadianceField] = None, compute_metrics: bool = False,
-           vis_indices: Optional[List[int]] = None, visualize: bool = False, feature_pca: Optional[dict] = None) -> Dict[str, list]:
+           vis_indices: Optional[List[int]] = None, visualize: bool = False, feature_pca: Optional[dict] = None,
+           to_host: bool = True) -> Dict[str, list]:
     """video_utils.py:109-468: the reference's result dictionary key for key -- the nine lists it always returns (possibly
     empty), the conditional ones (gt_rgbs, gt_sky_masks, shadow_*, forward_flows / backward_flows, median_depths), the
     scalars psnr, ssim, feat_psnr, masked_psnr, masked_ssim, masked_feat_psnr under the reference's rules (:206-247,421-428):
@@ -234,7 +242,13 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
     lo [3], hi [3]), "pe": (...)}) or, when None, from the first rendered image by ``get_robust_pca`` (sky zeroed, m = 2.5);
     they are returned under ``feature_pca`` so that a later call can colour another split consistently.  ``get_robust_pca`` is
     deterministic where the reference's ``torch.pca_lowrank`` is randomised: the colours follow the reference's formulas for
-    the same matrices, not its random draw.  Checked against tests/golden/flow_colours.npz / feature_colours.npz."""
+    the same matrices, not its random draw.  Checked against tests/golden/flow_colours.npz / feature_colours.npz.
+
+    ``to_host=False`` leaves the lists on the device: each holds the image's squeezed device tensors (the values and dtypes of
+    the host lists) and no image is transferred; the metrics are still read back once.  ``compose_video_frames`` /
+    ``save_videos`` take such lists and move 3 bytes per frame pixel instead of 4 to 12 bytes per pixel per list.  The cost is
+    device memory: every kept image (4 to 12 bytes per pixel per list, for all images of the loop) stays allocated until the
+    caller drops the lists."""
     always = ["rgbs", "static_rgbs", "dynamic_rgbs", "depths", "opacities", "static_depths", "static_opacities", "dynamic_depths",
               "dynamic_opacities"]
     out: Dict[str, list] = {v: [] for v in _COLLECT.values()}
@@ -306,6 +320,11 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
             # ONE device->host transfer per image: every kept tensor packed into a flat buffer, copied asynchronously into
             # pinned memory and unpacked while the NEXT image renders (the reference interleaves a blocking .cpu().numpy() per
             # key with the rendering; on a slow host that halves the loop's throughput)
+            if not to_host:     # the lists stay on the device
+                for name, t in keep.items():
+                    out[name].append(t.squeeze())
+                n_images += 1
+                continue
             pending.append(_pack_to_host(keep, pinned, n_images & 1))  # two alternating pinned buffers
             n_images += 1
             if len(pending) > 1:
@@ -344,6 +363,220 @@ def render(dataset, render_func: Callable, model: Optional[RadianceField] = None
                  ("masked_feat_psnr", masked_feat_psnrs)):
         out[k] = _non_zero_mean(v) if compute_metrics else -1
     return out
+
+
+# ------------------------------------------------------------------------------------------------ video frames
+def _frame_plan(render_results, keys, separate: bool):
+    """The rows of a frame as [(key, kind, image list, opacity list | None)] under the reference's rules (video_utils.py:525-553,
+    580-607): which list a key reads, which keys are skipped, what kind of tile its images become."""
+    plan = []
+    for key in keys:
+        if separate or key != "sky_masks":      # the separate mode asks for the key itself also when it then reads the opacities (:587)
+            if key not in render_results or len(render_results[key]) == 0:
+                continue
+        if key == "sky_masks":
+            plan.append((key, "one_minus_grey1", render_results["opacities"], None))
+        elif key == "gt_sky_masks":
+            plan.append((key, "grey1", render_results[key], None))
+        elif "depth" in key:
+            name = key.replace("depths", "opacities")
+            if name not in render_results:
+                if separate:
+                    raise KeyError(name)
+                if "median" not in key:
+                    continue
+                name = key.replace("median_depths", "opacities")
+            plan.append((key, "depth", render_results[key], render_results[name]))
+        else:
+            plan.append((key, "colour3", render_results[key], None))
+    return plan
+
+
+def _tile_image(x, kind: str, key: str, device) -> Tensor:
+    """One list entry as a device tensor of the tile's shape: numpy arrays are uploaded, anything not fp32 is converted."""
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not isinstance(t, Tensor):
+        raise ValueError(f"{key}: list entries are numpy arrays or tensors, not {type(x).__name__}")
+    ok = (t.dim() == 3 and t.shape[-1] == 3) if kind == "colour3" else t.dim() == 2
+    if not ok:
+        raise ValueError(f"{key}: images of shape {tuple(t.shape)} are neither [H, W, 3] colours nor one of the [H, W] cases "
+                         "(gt_sky_masks, sky_masks, depths with their opacities)")
+    return t.to(device=device, dtype=torch.float32, non_blocking=True)
+
+
+def compose_video_frames(render_results: Dict[str, list], num_timestamps: int, keys: List[str], num_cams: int, separate: bool = False,
+                         five_view_resize: bool = True):
+    """The 8-bit frames of the reference's ``save_concatenated_videos`` / ``save_seperate_videos`` (video_utils.py:507-627),
+    composed on the device: a generator of ``(i, frame)`` (``separate=False``: one merged frame per timestep, the keys' rows
+    stacked in the order of ``keys``) or ``(key, i, frame)`` (``separate=True``: key by key, one row each), ``frame`` a host uint8
+    array.  Per frame, each key's images ``[i * num_cams : (i + 1) * num_cams]`` lie side by side: colour lists as they are,
+    ``gt_sky_masks`` on three channels, ``sky_masks`` as 1 - opacity, a key containing ``depth`` coloured by
+    ``ops.compose_frame``'s depth rule with the opacity list named by replacing ``depths`` with ``opacities`` (``median_depths``
+    falls back to ``opacities``).  A key that is absent or empty is skipped; a depth key without an opacity list is skipped in
+    the merged mode and a ``KeyError`` in the separate one, as in the reference.  A merged frame that holds a depth row is
+    scaled by 255 in fp64, every other frame in fp32 (numpy's promotion in the reference; they differ at rounding ties only).
+
+    List entries are numpy arrays (uploaded frame by frame) or device tensors (``render(..., to_host=False)``).  ONE launch
+    builds a frame; only its 3 bytes per pixel leave the GPU, into one of two alternating pinned buffers, while the next frame
+    is composed.
+
+    Deviations from the reference: a NaN colour is written as 0 (numpy leaves that cast undefined); a group of exactly five
+    images raises ``NotImplementedError`` -- the reference shrinks the two outer views with a cubic-spline zoom
+    (``resize_five_views``), which is not implemented -- unless ``five_view_resize=False``, which tiles the five views
+    UNRESIZED; images that are neither [H, W, 3] nor one of the single-channel cases, or whose sizes differ within a frame,
+    raise ``ValueError``."""
+    plan = _frame_plan(render_results, keys, separate)
+    if not plan:
+        if separate:
+            return
+        raise ValueError(f"compose_video_frames: none of the keys {list(keys)} has images")
+    device = None
+    for _, _, images, opacities in plan:
+        for x in list(images[:1]) + list((opacities or [])[:1]):
+            if isinstance(x, Tensor) and x.is_cuda:
+                device = x.device
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    pinned: Dict[int, Tensor] = {}
+    n_frames = 0
+
+    def start(rows):
+        """Compose one frame of ``rows`` and start its transfer: (host view, event, the device frame)."""
+        nonlocal n_frames
+        tiles, H, W, cams = [], None, None, None
+        for r, (key, kind, images, opacities) in enumerate(rows):
+            if len(images) == 0 or (cams is not None and len(images) != cams):
+                raise ValueError(f"{key}: {len(images)} images in a frame" + ("" if cams is None else f" whose other rows have {cams}"))
+            cams = len(images)
+            if opacities is not None and len(opacities) < cams:
+                raise ValueError(f"{key}: {len(opacities)} opacity images for {cams} depth images")
+            for c, x in enumerate(images):
+                t = _tile_image(x, kind, key, device)
+                o = None if opacities is None else _tile_image(opacities[c], "depth", key, device)
+                if H is None:
+                    H, W = int(t.shape[0]), int(t.shape[1])
+                if tuple(t.shape[:2]) != (H, W) or (o is not None and tuple(o.shape) != (H, W)):
+                    raise ValueError(f"{key}: an image of {tuple(t.shape[:2])} in a frame of {(H, W)} images")
+                tiles.append((kind, r, c, t, o))
+        if cams == 5 and five_view_resize:
+            raise NotImplementedError("compose_video_frames: groups of five views are resized by the reference with a cubic-spline zoom "
+                                      "(resize_five_views), which is not implemented; pass five_view_resize=False to tile them unresized")
+        fp64 = (not separate) and any(kind == "depth" for _, kind, _, _ in rows)
+        frame = ops.compose_frame(tiles, H, W, len(rows), cams, fp64)
+        slot = n_frames & 1
+        n_frames += 1
+        buf = pinned.get(slot)
+        if buf is None or buf.numel() < frame.numel():
+            buf = pinned[slot] = torch.empty((frame.numel(),), dtype=torch.uint8, pin_memory=True)
+        host = buf[:frame.numel()].view(frame.shape)
+        host.copy_(frame, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev, frame
+
+    def finish(item) -> np.ndarray:
+        host, ev, _ = item
+        ev.synchronize()
+        return host.numpy().copy()      # the pinned buffer is reused two frames later
+
+    def cut(lst, i):
+        return lst[i * num_cams:(i + 1) * num_cams]
+
+    with torch.no_grad(), torch.cuda.device(device):
+        if separate:
+            jobs = [((key, i), [(key, kind, cut(images, i), None if opacities is None else cut(opacities, i))])
+                    for key, kind, images, opacities in plan for i in range(num_timestamps)]
+        else:
+            jobs = [((i,), [(key, kind, cut(images, i), None if opacities is None else cut(opacities, i)) for key, kind, images, opacities in plan])
+                    for i in range(num_timestamps)]
+        pending = None
+        for tag, rows in jobs:
+            item = (tag, start(rows))
+            if pending is not None:     # frame i leaves while frame i + 1 is composed
+                yield (*pending[0], finish(pending[1]))
+            pending = item
+        if pending is not None:
+            yield (*pending[0], finish(pending[1]))
+
+
+def _imageio():
+    try:
+        import imageio
+    except ImportError as e:
+        raise ImportError("save_videos writes through imageio, which is not installed; install it or pass writer_factory "
+                          "(and image_writer for save_images)") from e
+    return imageio
+
+
+def save_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int, keys: List[str] = ["gt_rgbs", "rgbs", "depths"],
+                num_cams: int = 3, save_seperate_video: bool = False, save_images: bool = False, fps: int = 10, verbose: bool = True,
+                writer_factory=None, image_writer=None, five_view_resize: bool = True):
+    """video_utils.py:471-504 on ``compose_video_frames``: the reference's signature (spelling included) and return value.
+    ``writer_factory(path, mode="I"[, fps=fps])`` returns an object with ``append_data(frame)`` and ``close()`` and
+    ``image_writer(path, image)`` writes one image; by default they are ``imageio.get_writer`` / ``imageio.imwrite``, imported
+    when first needed (``ImportError`` when imageio is absent).  ``five_view_resize``: see ``compose_video_frames``."""
+    fn = save_seperate_videos if save_seperate_video else save_concatenated_videos
+    return fn(render_results, save_pth, num_timestamps=num_timestamps, keys=keys, num_cams=num_cams, save_images=save_images, fps=fps,
+              verbose=verbose, writer_factory=writer_factory, image_writer=image_writer, five_view_resize=five_view_resize)
+
+
+def _open_writer(writer_factory, path: str, num_timestamps: int, fps: int):
+    factory = writer_factory if writer_factory is not None else _imageio().get_writer
+    return factory(path, mode="I") if num_timestamps == 1 else factory(path, mode="I", fps=fps)   # one timestep: it's an image
+
+
+def save_concatenated_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int,
+                             keys: List[str] = ["gt_rgbs", "rgbs", "depths"], num_cams: int = 3, save_images: bool = False, fps: int = 10,
+                             verbose: bool = True, writer_factory=None, image_writer=None, five_view_resize: bool = True):
+    """video_utils.py:507-565: one merged frame per timestep to one writer; returns ``{"concatenated_frame": frame}`` with the
+    frame at ``num_timestamps // 2`` (frame 0 of a single timestep).  ``save_images`` is ignored here, as in the reference."""
+    return_frame_id = 0 if num_timestamps == 1 else num_timestamps // 2
+    writer = _open_writer(writer_factory, save_pth, num_timestamps, fps)
+    return_frame = None
+    for i, frame in compose_video_frames(render_results, num_timestamps, keys, num_cams, False, five_view_resize):
+        if i == return_frame_id:
+            return_frame = frame
+        writer.append_data(frame)
+    writer.close()
+    if verbose:
+        logger.info(f"saved video to {save_pth}")
+    return {"concatenated_frame": return_frame}
+
+
+def save_seperate_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int,
+                         keys: List[str] = ["gt_rgbs", "rgbs", "depths"], num_cams: int = 3, fps: int = 10, verbose: bool = False,
+                         save_images: bool = False, writer_factory=None, image_writer=None, five_view_resize: bool = True):
+    """video_utils.py:568-627: one video per key at ``<save_pth>_<key>.mp4`` (or ``.png``); returns ``{key: frame}`` with each
+    key's frame at ``num_timestamps // 2``.  ``save_images`` also writes every view of every frame to
+    ``<save_pth>_<key>_<i * 3 + j>.png`` -- the reference's numbering, whatever ``num_cams`` is.  One deviation: no writer is
+    opened for a key that is then skipped (the reference opens one and leaves it)."""
+    import os
+    return_frame_id = num_timestamps // 2
+    return_frame_dict, writer, current, path = {}, None, None, None
+    for key, i, frame in compose_video_frames(render_results, num_timestamps, keys, num_cams, True, five_view_resize):
+        if key != current:
+            if writer is not None:
+                writer.close()
+                if verbose:
+                    logger.info(f"saved video to {path}")
+            path = save_pth.replace(".mp4", f"_{key}.mp4").replace(".png", f"_{key}.png")
+            writer, current = _open_writer(writer_factory, path, num_timestamps, fps), key
+        if save_images:
+            write = image_writer if image_writer is not None else _imageio().imwrite
+            if i == 0:
+                os.makedirs(path.replace(".mp4", ""), exist_ok=True)
+            n = len(render_results["opacities" if key == "sky_masks" else key][i * num_cams:(i + 1) * num_cams])
+            W = frame.shape[1] // n
+            for j in range(n):      # a view's 8-bit image is its columns of the row: every tile is cut to 8 bits on its own
+                write(path.replace(".mp4", f"_{i*3 + j:03d}.png"), np.ascontiguousarray(frame[:, j * W:(j + 1) * W]))
+        writer.append_data(frame)
+        if i == return_frame_id:
+            return_frame_dict[key] = frame
+    if writer is not None:
+        writer.close()
+        if verbose:
+            logger.info(f"saved video to {path}")
+    return return_frame_dict
 
 
 def _non_zero_mean(x: List[float]) -> float:

@@ -902,6 +902,36 @@ int emer_flow_colours(const emer_flow_colour_job *jobs, int32_t n_jobs, int64_t 
                       int32_t dark_background, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Video frames (radiance_fields/video_utils.py:471-627, utils/visualization_tools.py:30-33,79-156; csrc/frames.hip): ONE launch
+ * writes the tiles of a merged 8-bit frame, out uint8 [rows * H][cams * W][3], from fp32 device images.  A tile fills the cell
+ * (row, col) of the frame with its [H][W] image:
+ *   EMER_TILE_COLOUR3          src [H][W][3]: uint8(255 * clip(x, 0, 1)) per channel, truncating
+ *   EMER_TILE_GREY1            src [H][W]:    the same of x on all three channels
+ *   EMER_TILE_ONE_MINUS_GREY1  src [H][W]:    the same of 1 - x (one fp32 subtraction)
+ *   EMER_TILE_DEPTH            src, opacity [H][W]: t = -logf(x + 1e-6f) in fp32; in fp64 v = clip((t - depth_range[0]) /
+ *                              depth_range[1], 0, 1), NaN -> 0, p = v * opacity; the colour is row min(trunc(256 p), 255) of
+ *                              `table`, row 0 for p < 0, black for a NaN p
+ * fp64_scale != 0: the product 255 * clip(x) is formed in fp64 (the reference's frames that hold a depth row), else in fp32;
+ * a NaN colour is written as 0.  depth_range: two doubles ON THE HOST, min(lo', hi') and |hi' - lo'| of the curved bounds
+ * lo' = -log(lo + 1e-6), hi' = -log(hi + 1e-6).  table: 256 x 3 uint8 on the device (the 8-bit turbo colours).  Cells that no
+ * tile names are left as they are, so a frame of more than EMER_FRAME_TILES_MAX tiles takes several launches over disjoint
+ * tiles.  16-byte loads where W % 4 == 0 and a tile's bases are 16-byte aligned, dword stores where every group of four pixels
+ * starts on a dword of the frame; every path writes the same bytes, and a pixel's bytes depend on its own inputs, its kind and
+ * the flag alone.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMER_FRAME_TILES_MAX 48        /* 48 x 32 bytes by value: 1.5 KiB of the 4 KiB kernel-argument space */
+#define EMER_TILE_COLOUR3 0
+#define EMER_TILE_GREY1 1
+#define EMER_TILE_ONE_MINUS_GREY1 2
+#define EMER_TILE_DEPTH 3
+typedef struct emer_frame_tile {
+    const float *src, *opacity;        /* opacity: depth tiles only (ignored otherwise) */
+    int32_t kind, row, col, reserved;
+} emer_frame_tile;
+int emer_compose_frame(const emer_frame_tile *tiles, int32_t n_tiles, int32_t H, int32_t W, int32_t rows, int32_t cams,
+                       int32_t fp64_scale, const double *depth_range, const uint8_t *table, uint8_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Voxel lift of the feature field (utils/visualization_tools.py:456-701, csrc/voxels.hip): ray end points to occupied voxels,
  * density selectors and their gathers, all over BIT MASKS -- bit n lives in word n / 32 at position n % 32 of a uint32 buffer of
  * ceil(n_bits / 32) words.  A voxel grid of resolution res[3] has the linear index (ix * res[1] + iy) * res[2] + iz (the

@@ -145,6 +145,7 @@ SIGNATURES = {
     "emer_blend_over": [_P, c_int32, c_int64, _P],
     "emer_flow_colours": [_P, c_int32, c_int64, _P, c_float, c_int32, _P],
     "emer_compose_frame": [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P],
+    "emer_select": [_P, c_int32, c_int32, _P, _P, c_int32, c_int64, _P, _P],
     "emer_voxel_mark": [_P, c_int32, c_int64, _P],
     "emer_mean_threshold_bits": [_P, c_int32, c_int64, c_float, _P, _P],
     "emer_bits_offsets": [_P, c_int64, _P, _P],
@@ -165,6 +166,7 @@ INT64_FUNCTIONS = {
     "emer_ssim_workspace": [c_int32, c_int32],
     "emer_sq_err_sums_workspace": [c_int64, c_int32],
     "emer_bits_offsets_size": [c_int64],
+    "emer_select_workspace_bytes": [c_int32],
 }
 
 ALLOW_MISSING_SYMBOLS = False  # never set by the product path

@@ -52,6 +52,7 @@ class LidarSource:
         self.cached_indices: Optional[Tensor] = None
         self.cached_origins = self.cached_directions = self.cached_ranges = self.cached_normalized_timestamps = None
         self.seed_word = torch.tensor([seed], dtype=torch.int64, device=self.device)   # read by the kernel as uint64
+        self._aabb_seed = int(seed)                                                    # get_aabb's subset draw
 
     # ------------------------------------------------------------------------------------- timestamp registry (:139-221)
     @property
@@ -157,6 +158,27 @@ class LidarSource:
         sel = self.timesteps == time_idx
         return {"lidar_origins": self.origins[sel], "lidar_viewdirs": self.directions[sel], "lidar_ranges": self.ranges[sel],
                 "lidar_normed_timestamps": self.normalized_timestamps[sel]}
+
+    # ------------------------------------------------------------------------------------------- scene box (:103-138)
+    def get_aabb(self, lidar_downsample_factor: float = 4, lidar_percentile: float = 0.02, subset: Optional[Tensor] = None) -> Tensor:
+        """:103-138 -> the scene box [x0, y0, z0, x1, y1, z1] (fp32, on the device) from the lidar points ``origins + directions *
+        ranges``: a uniform subset of ``int(n / lidar_downsample_factor)`` points, then the ``lidar_percentile`` and ``1 -
+        lidar_percentile`` quantiles of every coordinate (``ops.quantile``: one radix select over the rows serves all six numbers,
+        without torch.quantile's sort and its limit of 16 777 216 elements), the upper z raised to 20 when it is lower.  ``subset``:
+        the indices to keep -- the reference's ``randperm(n)[: int(n / factor)]``, so that a recording of it can be replayed;
+        ``None`` draws them with a device ``randperm`` seeded by the source's seed (deterministic per seed, and independent of the
+        ray draws)."""
+        from . import ops
+        n = self.origins.shape[0]
+        pts = self.origins + self.directions * self.ranges.reshape(n, 1)
+        if subset is None:
+            g = torch.Generator(device=self.device).manual_seed(self._aabb_seed)
+            subset = torch.randperm(n, generator=g, device=self.device)[: int(n / lidar_downsample_factor)]
+        pts = pts[subset.to(self.device, torch.int64)].contiguous()
+        box = ops.quantile(pts, [lidar_percentile, 1 - lidar_percentile], dim=0)       # [2, 3]
+        aabb = box.reshape(6).clone()
+        aabb[5] = torch.where(aabb[5] < 20, torch.full_like(aabb[5], 20.0), aabb[5])
+        return aabb
 
     # -------------------------------------------------------------------------------------------- synthetic data
     @classmethod

@@ -1334,6 +1334,128 @@ def sq_err_sums(pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, out
     return res
 
 
+# ------------------------------------------------------------------------------------ order statistics (radix select)
+SELECT_JOBS_MAX = 16          # EMER_SELECT_JOBS_MAX
+SELECT_SOURCES_MAX = 4        # EMER_SELECT_SOURCES_MAX: distinct columns of one call
+SELECT_PER_SOURCE_MAX = 4     # EMER_SELECT_PER_SOURCE_MAX: distinct ranks / percentiles per column (a quantile takes two)
+SELECT_ROWS_MAX = 2 ** 31 - 1
+SELECT_VECTOR_ROWS = 1024     # rows that one workgroup takes per step on the 16-byte-load path (256 on the scalar path)
+SELECT_MAX_BLOCKS = 1024      # beyond it the workgroups stride over the rows
+_SEL_ORDER, _SEL_QUANTILE, _SEL_WPERCENT = 0, 1, 2
+
+
+class _SelectJob(ctypes.Structure):
+    """emer_select_job of include/emernerf_hip.h."""
+    _fields_ = [("column", ctypes.c_int32), ("output", ctypes.c_int32), ("param", ctypes.c_double), ("out", ctypes.c_void_p)]
+
+
+def _select(src: Tensor, n: int, stride: int, radius: bool, weights: Optional[Tensor], jobs, out_dtype) -> Tensor:
+    """``jobs``: a list of ``(column, output, param)`` over the contiguous fp32 ``src`` ([n * stride] elements) -> one value per job
+    (emer_select).  Requests beyond what one call takes (``SELECT_*_MAX``) are split into several calls."""
+    if not 1 <= n <= SELECT_ROWS_MAX:
+        raise _lib.EmerError(f"order statistics need 1 <= n < 2^31 rows, got {n}")
+    out = torch.empty(len(jobs), dtype=out_dtype, device=src.device)
+    item = out.element_size()
+    calls, cur, cols = [], [], {}
+    for i in sorted(range(len(jobs)), key=lambda k: jobs[k][0]):      # column by column: a call reads the rows once for all of them
+        col, output, param = jobs[i]
+        need = 2 if output == _SEL_QUANTILE else 1
+        if len(cur) == SELECT_JOBS_MAX or cols.get(col, 0) + need > SELECT_PER_SOURCE_MAX or (col not in cols and len(cols) == SELECT_SOURCES_MAX):
+            calls.append(cur)
+            cur, cols = [], {}
+        cols[col] = cols.get(col, 0) + need
+        cur.append((i, col, output, param))
+    calls.append(cur)
+    lib = _lib.load()
+    with torch.cuda.device(src.device):
+        ws = torch.empty(int(lib.emer_select_workspace_bytes(SELECT_JOBS_MAX)), dtype=torch.uint8, device=src.device)
+        for part in calls:
+            arr = (_SelectJob * len(part))()
+            for k, (i, col, output, param) in enumerate(part):
+                arr[k] = _SelectJob(int(col), output, float(param), out.data_ptr() + i * item)
+            _lib.call("emer_select", _ptr(src), 1 if radius else 0, stride, _ptr(weights), arr, len(part), n, _ptr(ws), _stream(src))
+    return out
+
+
+def _select_input(x: Tensor, dim: Optional[int]):
+    """-> (contiguous fp32 [n, C] view or copy, n, C, the shape of the other dimensions)."""
+    _check_cuda(x)
+    if not x.dtype.is_floating_point or x.dtype == torch.float64:
+        raise _lib.EmerError(f"order statistics are computed on fp32 keys: {x.dtype} is not supported")
+    if dim is None:
+        t = _f32c(x).reshape(-1, 1)
+        rest = ()
+    else:
+        moved = x.detach().movedim(dim, 0)
+        rest = tuple(moved.shape[1:])
+        t = _f32c(moved).reshape(moved.shape[0], -1)
+    return t, t.shape[0], t.shape[1], rest
+
+
+def _as_list(v, what: str):
+    if isinstance(v, Tensor):
+        if v.dim() > 1:
+            raise _lib.EmerError(f"{what}: a scalar or a 1-D sequence, got {tuple(v.shape)}")
+        return v.dim() == 0, [float(a) for a in v.reshape(-1).tolist()]
+    if isinstance(v, (int, float)):
+        return True, [float(v)]
+    return False, [float(a) for a in v]
+
+
+def order_statistics(x: Tensor, ranks, dim: Optional[int] = None) -> Tensor:
+    """The values of the 0-based ``ranks`` (an int or a sequence of ints) in ascending order of ``x`` along ``dim`` (``None``: of
+    the flattened tensor), ``sort(x, dim)[0][rank]`` without the sort (emer_select: an exact radix select, any size below 2^31
+    rows, the same bits from run to run).  NaN sorts last, -0 counts as +0 (a selected zero is +0).  Shape: ``[len(ranks), *rest]``,
+    or ``rest`` for a scalar rank; dtype and device follow ``x``."""
+    t, n, C, rest = _select_input(x, dim)
+    scalar, rs = _as_list(ranks, "ranks")
+    for r in rs:
+        if r != int(r) or not 0 <= r < n:
+            raise _lib.EmerError(f"order_statistics: rank {r} of {n} rows")
+    out = _select(t, n, C, False, None, [(c, _SEL_ORDER, r) for r in rs for c in range(C)], torch.float32)
+    out = out.reshape(len(rs), *rest).to(x.dtype)
+    return out[0] if scalar else out
+
+
+def quantile(x: Tensor, q, dim: Optional[int] = None, radius: bool = False) -> Tensor:
+    """``torch.quantile(x, q, dim=dim, interpolation="linear")`` for a scalar or 1-D ``q`` (a float, a sequence or a tensor) without
+    its sort and without its limit of 16 777 216 elements (emer_select): the rank ``float32(q) * float32(n - 1)`` in fp32, the two
+    neighbouring order statistics and torch's lerp, NaN if the input holds one.  ``radius=True``: ``x`` is a [..., 3] flow and the
+    quantile is taken over ``hypot(x[..., 0], x[..., 1])`` of all rows -- the expression the flow colour kernel evaluates -- without
+    materialising it.  Shape as torch's: the reduced shape for a scalar ``q``, ``[len(q), ...]`` for a 1-D one."""
+    scalar, qs = _as_list(q, "q")
+    for v in qs:
+        if not 0 <= v <= 1:
+            raise _lib.EmerError(f"quantile() q values must be in the range [0, 1], got {v}")
+    if radius:
+        _check_cuda(x)
+        t = _rows(x, 3, "quantile: flow")
+        out = _select(t, t.shape[0], 3, True, None, [(0, _SEL_QUANTILE, v) for v in qs], torch.float32).to(x.dtype)
+        return out[0] if scalar else out
+    t, n, C, rest = _select_input(x, dim)
+    out = _select(t, n, C, False, None, [(c, _SEL_QUANTILE, v) for v in qs for c in range(C)], torch.float32)
+    out = out.reshape(len(qs), *rest).to(x.dtype)
+    return out[0] if scalar else out
+
+
+def weighted_percentile(x: Tensor, w: Tensor, ps) -> Tensor:
+    """The reference's ``weighted_percentile(x, w, ps)`` (utils/visualization_tools.py:68-76) on the device, float64 [len(ps)]: the
+    values of ``x`` in ascending order against their cumulative weights, read at ``ps / 100`` of the total by linear interpolation.
+    Weights are clamped to [0, 1] and summed as integers of 2^-32, so the result is exact and the same from run to run (the
+    reference sums in fp32, in the order of an unstable argsort).  Equal values form ONE node with their summed weight: for
+    distinct values this is the reference in exact arithmetic; among tied values the reference's answer depends on the order its
+    argsort happens to give them and may differ.  ``w=None`` weighs every element 1."""
+    _check_cuda(x, w)
+    scalar, pl = _as_list(ps, "ps")
+    for p in pl:
+        if not 0 <= p <= 100:
+            raise _lib.EmerError(f"weighted_percentile: percentile {p} outside [0, 100]")
+    t = _f32c(x).reshape(-1)
+    wt = None if w is None else _per_row(w, t.numel(), "weighted_percentile: w")
+    out = _select(t, t.numel(), 1, False, wt, [(0, _SEL_WPERCENT, p) for p in pl], torch.float64)
+    return out[0] if scalar else out
+
+
 # ------------------------------------------------------------------------------------ evaluation colours
 COLOUR_JOBS_MAX = 8
 _TRANSITIONS = (15, 6, 4, 11, 13, 6)
@@ -1456,17 +1578,34 @@ def blend_over(a: Tensor, o: Tensor, b: Tensor) -> Tensor:
     return blend_over_multi([(a, o, b)])[0]
 
 
-def flow_colours_multi(flows, max_radius: Optional[float] = 1.0, background: str = "bright"):
+AUTO = "auto"      # a colour range taken from the data itself, as the reference's defaults (its ``None``) do
+
+
+def _is_auto(v) -> bool:
+    return isinstance(v, str) and v == AUTO
+
+
+def flow_colours_multi(flows, max_radius=1.0, background: str = "bright"):
     """The colour-wheel images of several [..., 3] flows of one shape as ONE launch (emer_flow_colours): the reference's
     ``scene_flow_to_rgb`` (hue from the angle of (x, y) by linear interpolation on the 55-step wheel, saturation ("bright") or
-    value ("dark") from the radius / max_radius, the other axis beyond radius 1), in [0, 1].  ``max_radius=None`` (the
-    reference's 99 % quantile rule) is not implemented."""
-    if max_radius is None:
-        raise NotImplementedError("flow_colours: max_radius=None (the quantile rule) is not implemented; pass a radius")
+    value ("dark") from the radius / max_radius, the other axis beyond radius 1), in [0, 1].  ``max_radius="auto"`` is the
+    reference's default rule (its ``flow_max_radius=None``): every flow is normalised by the 0.99 quantile of its own radius
+    (``quantile(flow, 0.99, radius=True)``, 4 bytes read to the host per flow, then one colour launch per flow); a quantile of 0
+    means no division.  ``max_radius=None`` itself keeps raising ``NotImplementedError``, as it always has here: the rule costs
+    a pass over the flow and a host read, so it is asked for by name."""
     if background not in ("bright", "dark"):
         raise ValueError(f"background should be one the following: ('bright', 'dark'), not {background}.")
     if not 1 <= len(flows) <= COLOUR_JOBS_MAX:
         raise _lib.EmerError(f"flow_colours: 1..{COLOUR_JOBS_MAX} flows, got {len(flows)}")
+    if max_radius is None:
+        raise NotImplementedError('flow_colours: max_radius=None is not a radius; pass one, or max_radius="auto" for the reference\'s '
+                                  "quantile rule")
+    if _is_auto(max_radius):
+        if any(f.shape != flows[0].shape for f in flows):
+            raise _lib.EmerError("flow_colours: the flows of one launch share the row count")
+        radii = [float(quantile(f, 0.99, radius=True)) for f in flows]
+        # a NaN quantile (a flow that holds a NaN) fails the reference's ``flow_max_radius > 0`` like a zero: no division
+        return [flow_colours_multi([f], r if r == r else 0.0, background)[0] for f, r in zip(flows, radii)]
     arr, keep, outs = (_FlowJob * len(flows))(), [], []
     n_rows = None
     for i, flow in enumerate(flows):
@@ -1487,7 +1626,7 @@ def flow_colours_multi(flows, max_radius: Optional[float] = 1.0, background: str
     return outs
 
 
-def flow_colours(flow: Tensor, max_radius: Optional[float] = 1.0, background: str = "bright") -> Tensor:
+def flow_colours(flow: Tensor, max_radius=1.0, background: str = "bright") -> Tensor:
     """``scene_flow_to_rgb(flow, flow_max_radius=max_radius, background=background)`` on the device (see ``flow_colours_multi``)."""
     return flow_colours_multi([flow], max_radius, background)[0]
 
@@ -1526,21 +1665,31 @@ def _turbo8_on(device) -> Tensor:
     return t
 
 
-def depth_range(lo: Optional[float] = 4.0, hi: Optional[float] = 120.0) -> Tuple[float, float]:
-    """``(min(lo', hi'), |hi' - lo'|)`` of the curved bounds ``lo' = -log(lo + 1e-6)``, ``hi' = -log(hi + 1e-6)`` in fp64 (no GPU
-    needed): the two constants of the depth colouring.  ``None`` is the reference's weighted-percentile rule, which needs a sort
-    of the image: not implemented."""
+def depth_range(lo=4.0, hi=120.0, depth: Optional[Tensor] = None, opacity: Optional[Tensor] = None) -> Tuple[float, float]:
+    """``(min(lo', hi'), |hi' - lo'|)`` of the curved bounds ``lo' = -log(lo + 1e-6)``, ``hi' = -log(hi + 1e-6)`` in fp64: the two
+    constants of the depth colouring (no GPU needed when both bounds are numbers).  A bound of ``"auto"`` is the reference's default
+    (its ``None``; ``visualize_cmap``, utils/visualization_tools.py:111-118) and needs the image: with ``lo_auto, hi_auto =
+    weighted_percentile(depth, opacity, [0.5, 99.5])`` (16 bytes read to the host), ``lo = lo or (lo_auto - eps32)`` and ``hi = hi
+    or (hi_auto + eps32)`` -- as there, a given bound of 0 is replaced too.  A bound of ``None`` itself keeps raising
+    ``NotImplementedError``, as it always has here: the rule costs five passes over the image and a host read, so it is asked
+    for by name."""
     import numpy as np
     if lo is None or hi is None:
-        raise NotImplementedError("depth colours: lo=None / hi=None (the weighted-percentile bounds, which need a sort) are not implemented; "
-                                  "pass both bounds")
+        raise NotImplementedError('depth colours: lo=None / hi=None are not bounds; pass both, or "auto" for the weighted-percentile '
+                                  "bounds of the image (ops.depth_colours, ops.depth_range with depth and opacity)")
+    if _is_auto(lo) or _is_auto(hi):
+        if depth is None or opacity is None:
+            raise ValueError('depth_range: a bound of "auto" is a weighted percentile of one image: pass its depth and opacity')
+        lo_auto, hi_auto = weighted_percentile(depth, opacity, [0.5, 99.5]).tolist()
+        eps = float(np.finfo(np.float32).eps)
+        lo = (None if _is_auto(lo) else lo) or (lo_auto - eps)
+        hi = (None if _is_auto(hi) else hi) or (hi_auto + eps)
     with np.errstate(all="ignore"):
         lo_c, hi_c = -np.log(np.float64(lo) + 1e-6), -np.log(np.float64(hi) + 1e-6)
     return float(np.minimum(lo_c, hi_c)), float(np.abs(hi_c - lo_c))
 
 
-def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool, lo: Optional[float] = 4.0,
-                  hi: Optional[float] = 120.0) -> Tensor:
+def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool, lo=4.0, hi=120.0) -> Tensor:
     """One merged 8-bit video frame, uint8 [rows * H, cams * W, 3], from device images (emer_compose_frame: ONE launch per
     ``FRAME_TILES_MAX`` tiles).  ``tiles`` is a list of ``(kind, row, col, src, opacity | None)``: ``src`` fills the cell
     (row, col) of the frame; ``kind`` is "colour3" (src [H, W, 3]: ``uint8(255 * clip(x, 0, 1))``), "grey1" (src [H, W] on three
@@ -1548,8 +1697,15 @@ def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool,
     the bounds ``lo``, ``hi`` -- ``-log(x + 1e-6)`` scaled to [0, 1] between the curved bounds, times the opacity, as a row of
     the turbo table).  ``fp64_scale``: the product with 255 in fp64, as in the reference's frames that hold a depth row.  A NaN
     colour is written as 0.  Sources may be views with a storage offset; anything that is not contiguous fp32 is copied.  Cells
-    that no tile names are zero.  A pixel's bytes depend on its own inputs, the kind and the flag alone."""
-    dmin, dabs = depth_range(lo, hi)
+    that no tile names are zero.  A pixel's bytes depend on its own inputs, the kind and the flag alone.  A bound of ``"auto"``
+    is the weighted-percentile bound of the frame's ONE depth tile (``depth_range``); a launch has one range, so with any other
+    number of depth tiles ``"auto"`` raises.  ``None`` raises as it always has."""
+    auto = (_is_auto(lo) or _is_auto(hi)) and lo is not None and hi is not None
+    if auto and sum(1 for t in tiles if t[0] == "depth") != 1:
+        raise NotImplementedError('compose_frame: a bound of "auto" is a weighted percentile of one depth image and a launch has one '
+                                  "range: implemented for a frame with exactly one depth tile; pass both bounds otherwise")
+    if not auto:
+        dmin, dabs = depth_range(lo, hi)
     H, W, rows, cams = int(H), int(W), int(rows), int(cams)
     if not tiles:
         raise ValueError("compose_frame: no tiles")
@@ -1570,6 +1726,9 @@ def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool,
         cells.add((int(row), int(col)))
         arr[i] = _FrameTile(s.data_ptr(), None if o is None else o.data_ptr(), TILE_KINDS[kind], int(row), int(col), 0)
     ref = keep[0][0]
+    if auto:
+        d, o = next(k for k, t in zip(keep, tiles) if t[0] == "depth")
+        dmin, dabs = depth_range(lo, hi, d, o)
     shape = (rows * H, cams * W, 3)
     out = (torch.empty if len(cells) == rows * cams else torch.zeros)(shape, dtype=torch.uint8, device=ref.device)
     rng = (ctypes.c_double * 2)(dmin, dabs)
@@ -1583,9 +1742,10 @@ def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool,
     return out
 
 
-def depth_colours(depth: Tensor, opacity: Tensor, lo: Optional[float] = 4.0, hi: Optional[float] = 120.0) -> Tensor:
+def depth_colours(depth: Tensor, opacity: Tensor, lo=4.0, hi=120.0) -> Tensor:
     """The reference's ``depth_visualizer`` cut to 8 bits, uint8 [H, W, 3], of a [H, W] depth and opacity: a one-tile frame
-    (see ``compose_frame``)."""
+    (see ``compose_frame``).  ``lo`` / ``hi`` of ``"auto"`` are the reference's defaults (its ``None``): the image's own weighted-percentile
+    bounds (``depth_range``)."""
     if depth.dim() != 2:
         raise ValueError(f"depth_colours: expected a [H, W] depth, got {tuple(depth.shape)}")
     H, W = depth.shape

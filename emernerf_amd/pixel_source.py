@@ -373,6 +373,24 @@ class PixelSource:
     def __len__(self) -> int:
         return self.num_imgs
 
+    # -------------------------------------------------------------------------------------------- scene box (:391-437)
+    def get_aabb(self, num_cams: Optional[int] = None) -> Tensor:
+        """:391-437 -> the coarse scene box [x0, y0, z0, x1, y1, z1] (fp32, on the device) from the FRONT camera's trajectory: its
+        position range, extended by 40 m along x and y, by 20 m upwards (capped at 20) and 5 m downwards (at least down to -5).
+        The front camera is image 0, 1, 2 or 2 of every group of 1, 3, 5 or 6 cameras (the orders of the reference's loaders).
+        ``num_cams``: default the number of distinct ``cam_ids`` (1 without them).  Plain torch: a handful of numbers once per
+        run; the dataset picks this box or the lidar one (``LidarSource.get_aabb``)."""
+        if num_cams is None:
+            num_cams = 1 if self.cam_ids is None else int(self.cam_ids.unique().numel())
+        front = {1: 0, 3: 1, 5: 2, 6: 2}.get(int(num_cams))
+        if front is None:
+            raise ValueError(f"get_aabb: the front camera is known for 1, 3, 5 or 6 cameras, not {num_cams}")
+        pos = self.cam_to_worlds[front::int(num_cams), :3, 3]
+        lo, hi = pos.min(dim=0)[0], pos.max(dim=0)[0]
+        hi = torch.stack([hi[0] + 40, hi[1] + 40, torch.clamp(hi[2] + 20, max=20.0)])
+        lo = torch.stack([lo[0] - 40, lo[1] - 40, torch.clamp(lo[2] - 5, min=-5.0)])
+        return torch.cat([lo, hi])
+
     def __getitem__(self, idx: int) -> Dict[str, Tensor]:
         return self.get_render_rays(idx)
 

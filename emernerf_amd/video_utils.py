@@ -24,7 +24,8 @@ deterministic.
 8-bit frames the reference logs and writes: ``compose_video_frames`` builds each merged frame -- the keys' rows, the turbo
 depth colouring, the cut to 8 bits -- in ONE launch of csrc/frames.hip, so that with ``render(..., to_host=False)`` only
 3 bytes per frame pixel leave the GPU.  Out of scope here: the video encoding itself (imageio's, or the caller's writer),
-the weighted-percentile depth bounds (``lo`` / ``hi`` of None) and ``resize_five_views`` (groups of five views raise unless
+the weighted-percentile depth bounds inside a merged frame (the loop passes 4 / 120 as the reference's does; one image's own
+bounds are ``ops.depth_colours(depth, opacity, "auto", "auto")``) and ``resize_five_views`` (groups of five views raise unless
 they are tiled unresized).
 """
 from __future__ import annotations

@@ -932,6 +932,49 @@ int emer_compose_frame(const emer_frame_tile *tiles, int32_t n_tiles, int32_t H,
                        int32_t fp64_scale, const double *depth_range, const uint8_t *table, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Order statistics (csrc/select.hip): the k-th smallest value, torch.quantile's linear rule and the weighted percentile of
+ * utils/visualization_tools.py:68-76 over ONE fp32 device array of n rows, by an exact radix select -- no sort, no size limit
+ * below 2^31 rows, integer sums only, so the results are identical from run to run.
+ *   sources  EMER_SELECT_COLUMNS: the column `column` of a row-major [n][stride] array (stride 1: a contiguous [n]);
+ *            EMER_SELECT_RADIUS:  hypotf(row[0], row[1]) of an [n][3] array (stride 3; `column` is ignored).
+ *            -0 counts as +0; a NaN sorts last and marks its source.
+ *   weights  [n] fp32 or NULL.  Each weight is clamped to [0, 1] (NaN: 0) and counts as the integer rint(w * 2^32); without
+ *            weights every row counts 1.  With weights every job must be EMER_SELECT_WPERCENT.
+ *   jobs     EMER_SELECT_ORDER:    out (float *) = the value of rank param (0-based, integral, < n);
+ *            EMER_SELECT_QUANTILE: out (float *) = torch.quantile(source, param), interpolation "linear": rank = float(param) *
+ *                                  float(n - 1) in fp32, a / b the values of rank floor / ceil (clamped to n - 1), w = rank -
+ *                                  floor, d = b - a, fmaf(w, d, a) for w < 0.5 else fmaf(-d, 1 - w, b); NaN if the source holds one;
+ *            EMER_SELECT_WPERCENT: out (double *) = the weighted percentile param (0 .. 100) with equal values merged into one
+ *                                  node: t = param * (total / 100) in fp64 from the integer total; hi = the smallest value whose
+ *                                  cumulative weight exceeds t (none: the largest value, whatever its weight), lo = the largest
+ *                                  value below hi, whatever its weight (none: hi is returned); lo + (t - cum(<= lo)) /
+ *                                  (cum(<= hi) - cum(<= lo)) * (hi - lo) in fp64, each operation rounded on its own.
+ * One call serves up to EMER_SELECT_JOBS_MAX jobs over up to EMER_SELECT_SOURCES_MAX distinct columns with up to
+ * EMER_SELECT_PER_SOURCE_MAX distinct ranks / percentiles each (a quantile takes two ranks); EMER_E_INVALID beyond.  Four
+ * histogram launches (8-bit digits, most significant first), one more for the weighted percentile's lower neighbour, one that
+ * writes the outputs; the launch boundary is the only synchronisation between workgroups.  workspace:
+ * emer_select_workspace_bytes(n_jobs) bytes, 16-byte aligned; the call clears it on the stream.  It neither allocates nor
+ * synchronises.  16-byte loads for stride 1 and 3 when src (and weights) are 16-byte aligned; every path gives the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define EMER_SELECT_JOBS_MAX 16
+#define EMER_SELECT_SOURCES_MAX 4
+#define EMER_SELECT_PER_SOURCE_MAX 4
+#define EMER_SELECT_COLUMNS 0
+#define EMER_SELECT_RADIUS 1
+#define EMER_SELECT_ORDER 0
+#define EMER_SELECT_QUANTILE 1
+#define EMER_SELECT_WPERCENT 2
+#define EMER_SELECT_ROWS_MAX 2147483647ll
+typedef struct emer_select_job {
+    int32_t column, output;
+    double param;
+    void *out;
+} emer_select_job;
+int64_t emer_select_workspace_bytes(int32_t n_jobs);
+int emer_select(const float *src, int32_t source_kind, int32_t stride, const float *weights, const emer_select_job *jobs,
+                int32_t n_jobs, int64_t n, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Voxel lift of the feature field (utils/visualization_tools.py:456-701, csrc/voxels.hip): ray end points to occupied voxels,
  * density selectors and their gathers, all over BIT MASKS -- bit n lives in word n / 32 at position n % 32 of a uint32 buffer of
  * ceil(n_bits / 32) words.  A voxel grid of resolution res[3] has the linear index (ix * res[1] + iy) * res[2] + iz (the

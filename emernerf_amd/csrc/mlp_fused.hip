@@ -662,6 +662,22 @@ __device__ __forceinline__ void park_rows(u32x2 *park, const Opd<(KT0 + 1) / 2> 
     }
 }
 
+// The wait of a tile loop for the inputs it prefetched one tile ago.  The loops below issue the PREVIOUS tile's stores right behind this
+// wait, so that a store has a whole tile to drain.  The compiler does not read inline assembly: a register that the prefetch loaded is,
+// for it, still in flight at its first use, and because vmcnt counts loads and stores alike (and not in order between the two kinds) it
+// waits there for vmcnt(0) -- behind the stores, that is for their write acknowledgement, once per tile.  Passing the prefetched
+// registers THROUGH the wait makes them its results: the compiler's own wait then stands in front of this one, where nothing is in
+// flight that the loop does not wait for anyway, and none follows the stores.
+#define EMER_WAIT_VM0_2(a, b) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b)::"memory")
+template <int KT>
+__device__ __forceinline__ void wait_vm0(f32x4 (&x)[KT], float &a, float &b) {
+    static_assert(KT >= 1 && KT <= 4, "one operand per 16-feature input tile");
+    if constexpr (KT == 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(a), "+v"(b)::"memory");
+    if constexpr (KT == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(a), "+v"(b)::"memory");
+    if constexpr (KT == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(a), "+v"(b)::"memory");
+    if constexpr (KT == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(a), "+v"(b)::"memory");
+}
+
 constexpr int neckw_threads(int kt0, int no = 1) { return no == 2 ? 256 : 512; }
 // (512 threads = 8 waves, ONE workgroup per CU = 2 waves per SIMD, <= 256 registers; the weights, 48-72 KB, are staged once per CU and
 // leave room for 7-10 KB of per-wave staging)
@@ -700,6 +716,10 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
     // where the 16 x 16 x 16 shape needed four at the same issue cost each; operands: two transposer outputs joined by v_permlane16_swap,
     // see block32): lane (j, h), register r = dW[32 P + 8 (r >> 2) + 4 h + (r & 3)][32 Q + j]
     constexpr int QB = (KT0 + 1) / 2;   // 32-feature blocks of the encoding (the last one half empty when KT0 is odd)
+    // The prefetched registers pass through the tile's wait (wait_vm0) up to 32 input features.  The wider 64-output instantiations
+    // spill (104-292 bytes per lane), their scratch reloads count in vmcnt too and stand in the middle of the tile: with a prefetch
+    // that really is in flight there, <3, 2, 1> ran 5 % SLOWER than with the compiler's early wait, so they keep the plain wait.
+    constexpr bool kThroughWait = KT0 <= 2;
     f32x16 bw1[2 * NO][2], bw0[2][QB];
     float ab1[4 * NO], ab0[4];      // bias gradients: this lane's rows 4 g .. 4 g + 3 of feature 16 p + m
     zero_blocks(bw1);
@@ -753,7 +773,8 @@ __global__ __launch_bounds__((neckw_threads(KT0, NO)), (neckw_threads(KT0, NO) =
     int64_t tile_prev = -1;
     for (int64_t tile = t_begin; tile < t_end; ++tile) {
         Raw cur;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's inputs have landed (issued one tile ago)
+        if constexpr (kThroughWait) wait_vm0<KT0>(xn, ddn, den);   // this tile's inputs have landed (issued one tile ago)
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (tile_prev >= 0) st_lm_t<KT0, F>(a.denc + tile_prev * 16 * F, (unsigned)a.n, a.n_levels, (unsigned)m, tile_prev * 16 + m < a.n, g, dep);
 #pragma unroll
         for (int p = 0; p < 4; ++p)
@@ -1324,14 +1345,18 @@ __device__ __forceinline__ void rgb_w_store_dgeo(float *dgeo_prev, const f32x4 (
 // twelve stages of twelve matrix instructions (two output tiles x one k-step x six partial products); every stage first issues the
 // NEXT stage's weight-fragment reads (the last one of a tile: the first stage of whatever follows, `wnext`), then its matrix
 // instructions, then a share of the vector work that does not depend on them -- the output layer's weight gradient next to the first
-// GEMM, the masking / splitting of d0 next to dgeo's d1 half, and next to its d0 half the caller's `side(0..3)` (rgb_bwdw16_kernel: the
-// split + transposition of the B operands a1, geo).  EMER_RGBW_SB() pins the stage order; inside a stage the scheduler is free.
+// GEMM, the masking / splitting of d0 next to dgeo's d1 half, and from its last stage on the caller's `side(0..3, .)` (rgb_bwdw16_kernel:
+// the split + transposition of the B operands a1, geo, each read from LDS one stage ahead of its split).  EMER_RGBW_SB() pins the stage
+// order; inside a stage the scheduler is free.
 // In: fa = fragments (w1a, 0, 0), d2 = dpre2 of (row m, channel g), m2 = a2 (relu mask and operand of dW2), a1_mask(m1) fills the relu
 // mask of d0 when it is needed.  Out: d1o / d0o = dpre1 / dpre0 as chain operands, dg = dgeo, fa = fragments (wnext, 0, 0).
 template <class A1Mask, class Side>
 __device__ __forceinline__ void rgb_w_chain(RgbWAcc &st, const RgbWLane &L, Frag6 &fa, Frag6 &fb, const W3 wnext, float d2, const f32x4 (&m2)[4],
                                             A1Mask a1_mask, Side side, Opd<2> &d1o, Opd<2> &d0o, f32x4 (&dg)[4]) {
     const int m = L.m;
+    // (one wave per SIMD: an LDS result that is used right behind its read costs the read's whole latency, so whatever goes through LDS is
+    // asked for a stage ahead of its use -- the three lane shuffles of dW2 here, the mask of d0 in stage 3, the caller's side reads)
+    const float dc[3] = {__shfl(d2, m, 64), __shfl(d2, 16 + m, 64), __shfl(d2, 32 + m, 64)};
     {
         f32x4 d1[4];
         zero<4>(d1);
@@ -1341,28 +1366,25 @@ __device__ __forceinline__ void rgb_w_chain(RgbWAcc &st, const RgbWLane &L, Frag
         make_opd<4>(d1, d1o);
     }
     EMER_RGBW_SB();
-    f32x4 d0[4];
+    f32x4 d0[4], m1[4];
     zero<4>(dg); zero<4>(d0);
     // ---- GEMM 1: d0 = W1a^T d1 (stages 0-3) next to dW2 / db2
     ld_frag6(fb, L.w1a, 0, 1); mma_frag6<2>(fa, d1o, 0, d0[0], d0[1]);
     st.b2acc += d2;
-    { const float dc = __shfl(d2, m, 64); st.w2acc[0] += row16_reduce_scatter(m2, dc, m); }
+    st.w2acc[0] += row16_reduce_scatter(m2, dc[0], m);
     EMER_RGBW_SB();
     ld_frag6(fa, L.w1a, 1, 0); mma_frag6<2>(fb, d1o, 0, d0[2], d0[3]);
-    { const float dc = __shfl(d2, 16 + m, 64); st.w2acc[1] += row16_reduce_scatter(m2, dc, m); }
+    st.w2acc[1] += row16_reduce_scatter(m2, dc[1], m);
     EMER_RGBW_SB();
     ld_frag6(fb, L.w1a, 1, 1); mma_frag6<2>(fa, d1o, 1, d0[0], d0[1]);
-    { const float dc = __shfl(d2, 32 + m, 64); st.w2acc[2] += row16_reduce_scatter(m2, dc, m); }
+    st.w2acc[2] += row16_reduce_scatter(m2, dc[2], m);
     EMER_RGBW_SB();
-    ld_frag6(fa, L.w1g, 0, 0); mma_frag6<2>(fb, d1o, 1, d0[2], d0[3]);
+    ld_frag6(fa, L.w1g, 0, 0); a1_mask(m1);
+    mma_frag6<2>(fb, d1o, 1, d0[2], d0[3]);
     EMER_RGBW_SB();
     // ---- GEMM 2: dgeo += W1g^T d1 (stages 4-7) next to the mask and split of d0
     ld_frag6(fb, L.w1g, 0, 1); mma_frag6<2>(fa, d1o, 0, dg[0], dg[1]);
-    {
-        f32x4 m1[4];
-        a1_mask(m1);
-        relu_mask<4>(d0, m1);
-    }
+    relu_mask<4>(d0, m1);
     EMER_RGBW_SB();
     ld_frag6(fa, L.w1g, 1, 0); mma_frag6<2>(fb, d1o, 0, dg[2], dg[3]);
     set_kstep(d0o, 0, d0[0], d0[1]);
@@ -1370,20 +1392,24 @@ __device__ __forceinline__ void rgb_w_chain(RgbWAcc &st, const RgbWLane &L, Frag
     ld_frag6(fb, L.w1g, 1, 1); mma_frag6<2>(fa, d1o, 1, dg[0], dg[1]);
     set_kstep(d0o, 1, d0[2], d0[3]);
     EMER_RGBW_SB();
-    ld_frag6(fa, L.w0, 0, 0); mma_frag6<2>(fb, d1o, 1, dg[2], dg[3]);
+    ld_frag6(fa, L.w0, 0, 0); side(0, false);
+    mma_frag6<2>(fb, d1o, 1, dg[2], dg[3]);
     EMER_RGBW_SB();
-    // ---- GEMM 3: dgeo += W0g^T d0 (stages 8-11) next to the caller's side work
-    ld_frag6(fb, L.w0, 0, 1); mma_frag6<2>(fa, d0o, 0, dg[0], dg[1]);
-    side(0);
+    // ---- GEMM 3: dgeo += W0g^T d0 (stages 8-11) next to the caller's side work: side(k, false) asks LDS for what side(k, true) works on
+    ld_frag6(fb, L.w0, 0, 1); side(1, false);
+    mma_frag6<2>(fa, d0o, 0, dg[0], dg[1]);
+    side(0, true);
     EMER_RGBW_SB();
-    ld_frag6(fa, L.w0, 1, 0); mma_frag6<2>(fb, d0o, 0, dg[2], dg[3]);
-    side(1);
+    ld_frag6(fa, L.w0, 1, 0); side(2, false);
+    mma_frag6<2>(fb, d0o, 0, dg[2], dg[3]);
+    side(1, true);
     EMER_RGBW_SB();
-    ld_frag6(fb, L.w0, 1, 1); mma_frag6<2>(fa, d0o, 1, dg[0], dg[1]);
-    side(2);
+    ld_frag6(fb, L.w0, 1, 1); side(3, false);
+    mma_frag6<2>(fa, d0o, 1, dg[0], dg[1]);
+    side(2, true);
     EMER_RGBW_SB();
     ld_frag6(fa, wnext, 0, 0); mma_frag6<2>(fb, d0o, 1, dg[2], dg[3]);
-    side(3);
+    side(3, true);
     EMER_RGBW_SB();
 }
 
@@ -1485,13 +1511,17 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
     // 16 p + j -- which sits at float 256 p + 4 (row + 16 (j >> 2)) + (j & 3) of the lane-major tile.  Four strided LDS reads and two
     // exact splits per 16-feature tile replace (per tensor) one operand split of the chain layout, four transposer passes through the
     // matrix pipe and their 48 accumulator read-backs: the matrix core only has to transpose what it produced itself (dpre1, dpre0).
-    auto b_tile = [&](const float *tile, int p) -> SwT {
+    // The reads go out one stage ahead of the splits: with nothing else on the SIMD a split right behind its read sat out the LDS
+    // latency, eight times per tile.
+    auto b_read = [&](const float *tile, int p, float (&v)[4]) {
         const float *q = tile + 256 * p + 64 * (m >> 2) + (m & 3) + 16 * g;   // row 4 g (+ i below: 4 floats further per row)
-        const float v0 = q[0], v1 = q[4], v2 = q[8], v3 = q[12];
+        v[0] = q[0]; v[1] = q[4]; v[2] = q[8]; v[3] = q[12];
+    };
+    auto b_tile = [&](const float (&v)[4]) -> SwT {
         SwT t;
         unsigned h0, m0, l0, h1, m1, l1;
-        split3(v0, v1, h0, m0, l0);
-        split3(v2, v3, h1, m1, l1);
+        split3(v[0], v[1], h0, m0, l0);
+        split3(v[2], v[3], h1, m1, l1);
         t.h = u32x2{h0, h1}; t.m = u32x2{m0, m1}; t.l = u32x2{l0, l1};
         return t;
     };
@@ -1514,7 +1544,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
         float s1c[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s0c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < tpr; ++j) {
             float *dgeo = a.dgeo + ((ray * tpr + j) * 16) * 64;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            EMER_WAIT_VM0_2(yn, dn);
             rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
             f32x4 m2[4];
 #pragma unroll
@@ -1531,14 +1561,20 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdw16_kernel(const RgbBwdW
             Opd<2> d1o, d0o;
             f32x4 dg[4];
             SwP Bq[4];
+            float braw[2][2][4];   // [k & 1][tile of the pair]: what side(k, false) read for side(k, true)
             rgb_w_chain(st, L, fa, fb, L.w1a, d2, m2,
                         [&](f32x4 (&m1)[4]) {   // a1 from the staged tile, read only here: the mask is not live across GEMM 1
 #pragma unroll
                             for (int p = 0; p < 4; ++p) m1[p] = *reinterpret_cast<const f32x4 *>(sb + 256 * p + 4 * lane);
                         },
-                        [&](int k) {   // the B operands of the dW products: a1 (k = 0, 1), geo (k = 2, 3)
-                            const float *t = sb + 1024 * (k >> 1);
-                            Bq[k] = block32(b_tile(t, 2 * (k & 1)), b_tile(t, 2 * (k & 1) + 1));
+                        [&](int k, bool work) {   // the B operands of the dW products: a1 (k = 0, 1), geo (k = 2, 3)
+                            if (!work) {
+                                const float *t = sb + 1024 * (k >> 1);
+                                b_read(t, 2 * (k & 1), braw[k & 1][0]);
+                                b_read(t, 2 * (k & 1) + 1, braw[k & 1][1]);
+                            } else {
+                                Bq[k] = block32(b_tile(braw[k & 1][0]), b_tile(braw[k & 1][1]));
+                            }
                         },
                         d1o, d0o, dg);
 #pragma unroll
@@ -1629,7 +1665,8 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
         float s1c[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s0c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < tpr; ++j) {
             float *dgeo = a.dgeo + ((ray * tpr + j) * 16) * 64;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm0<4>(xg, yn, dn);   // (see EMER_WAIT_VM0_2; behind it nothing is in flight, so the second statement waits for nothing)
+            if constexpr (A1_STORED) asm volatile("" : "+v"(ag[0]), "+v"(ag[1]), "+v"(ag[2]), "+v"(ag[3])::"memory");
             rgb_w_store_dgeo(dgeo_prev, dgp, L.lo64);
             f32x4 x[4], a1[4], a2[4];
 #pragma unroll
@@ -1733,7 +1770,7 @@ __global__ __launch_bounds__(kRWThreads, 1) void rgb_bwdwr_kernel(const RgbBwdRA
 #pragma unroll
                             for (int p = 0; p < 4; ++p) m1[p] = a1[p];
                         },
-                        [](int) {}, d1o, d0o, dg);
+                        [](int, bool) {}, d1o, d0o, dg);
 #pragma unroll
             for (int p = 0; p < 4; ++p) dgp[p] = dg[p];
             dgeo_prev = dgeo;

@@ -152,6 +152,19 @@ def kernel_case(kernel):
         full = H.rgb_head_fwd(c)
         o = H.rgb_head_bwd(c, full, False)
         return lambda call: H.rgb_head_bwd(c, full, False, call=call, o=o)
+    if name in ("rgb_bwdw16_kernel", "rgb_bwdwr_kernel"):   # (with their reduction launch, which is the same code in both libraries)
+        c = H.rgb_case(R, S)
+        full = H.rgb_head_fwd(c)
+        Kh, p = c["Kh"], H._ptr
+        ws = H.buf(int(_lib.load().emer_rgb_head_bwd_fused_workspace(R, S)))
+        o = dict(dgeo=H.buf(N, 64), s1=H.buf(R, 64), s0=H.buf(R, 64), dw0=H.buf(64, Kh + 64), dw1=H.buf(64, 128 + Kh), dw2=H.buf(3, 64), db2=H.buf(3))
+        tail = (Kh, p(c["w0"]), p(c["w1"]), p(c["w2"]), p(o["dgeo"]), p(o["s1"]), p(o["s0"]), p(ws), p(o["dw0"]), Kh + 64, p(o["dw1"]), 128 + Kh,
+                p(o["dw2"]), 64, p(o["db2"]), H._stream(c["geo"]))
+        if name == "rgb_bwdw16_kernel":
+            return lambda call: call("emer_rgb_head_bwd_fused", p(c["dout"]), p(full["out"]), p(full["a1"]), p(full["a2"]), p(c["geo"]), 64, R, S, *tail)
+        a1 = p(full["a1"]) if t and t[0] else None   # <true>: a1 stored by the forward, <false>: recomputed too
+        return lambda call: call("emer_rgb_head_bwd_recompute", p(c["dout"]), p(full["out"]), a1, p(c["geo"]), 64, p(c["rb"]), p(c["rb"][:, 64:]), 128,
+                                 R, S, *tail)
     if name == "field_fwd_kernel":
         c = H.rgb_case(R, S, 49, level(t[0], t[1]), t[1])
         o = H.field_fwd(c)

@@ -486,7 +486,7 @@ union RayJobDev {
     emer_ray_wgrad_args wgrad;
     emer_embed_grad_args embed_grad;
     DwReduceDev dw_reduce;
-    struct { emer_ray_inputs_args in; emer_ray_pre_fwd_args pre; emer_ray_head_fwd_args head; } fwd_chain;
+    struct { emer_ray_inputs_args inp; emer_ray_pre_fwd_args pre; emer_ray_head_fwd_args head; } fwd_chain;
     struct { emer_ray_head_bwd_args head; emer_ray_pre_bwd_args pre; } bwd_chain;
 };
 struct RayJobsDev {
@@ -532,8 +532,8 @@ __device__ __forceinline__ void ray_jobs_body(const RayJobsDev &J) {
         break;
     }
     case EMER_RAY_JOB_FWD_CHAIN: {
-        const int64_t r0 = lb * kRayTile, R = U.fwd_chain.in.n_rays;
-        ray_inputs_stage(U.fwd_chain.in, r0, r0 + kRayTile < R ? r0 + kRayTile : R, threadIdx.x, kRayThreads);
+        const int64_t r0 = lb * kRayTile, R = U.fwd_chain.inp.n_rays;
+        ray_inputs_stage(U.fwd_chain.inp, r0, r0 + kRayTile < R ? r0 + kRayTile : R, threadIdx.x, kRayThreads);
         __syncthreads();
         ray_pre_fwd_stage(U.fwd_chain.pre, r0, lds_f);
         if (J.n_stages[j] > 2) {
@@ -760,18 +760,18 @@ extern "C" int emer_ray_jobs(const emer_ray_job *jobs, int32_t n_jobs, void *str
             const auto &C = q.u.fwd_chain;
             n_stages = q.n_stages;
             EMER_REQUIRE(n_stages == 2 || n_stages == 3, "ray_jobs: job %d: a forward chain has 2 or 3 stages", i);
-            if (int rc = check_ray_inputs(C.in)) return rc;
+            if (int rc = check_ray_inputs(C.inp)) return rc;
             if (int rc = check_ray_pre_fwd(C.pre)) return rc;
-            EMER_REQUIRE(C.pre.n_rays == C.in.n_rays, "ray_jobs: job %d: the stages of a chain share the row count", i);
-            U.fwd_chain.in = C.in; U.fwd_chain.pre = C.pre;
+            EMER_REQUIRE(C.pre.n_rays == C.inp.n_rays, "ray_jobs: job %d: the stages of a chain share the row count", i);
+            U.fwd_chain.inp = C.inp; U.fwd_chain.pre = C.pre;
             need = ray_pre_fwd_lds(C.pre.kh);
             if (n_stages == 3) {
                 if (int rc = check_ray_head_fwd(C.head)) return rc;
-                EMER_REQUIRE(C.head.n_rows == C.in.n_rays, "ray_jobs: job %d: the stages of a chain share the row count", i);
+                EMER_REQUIRE(C.head.n_rows == C.inp.n_rays, "ray_jobs: job %d: the stages of a chain share the row count", i);
                 U.fwd_chain.head = C.head;
                 if (need < kHeadFwdLds * sizeof(float)) need = kHeadFwdLds * sizeof(float);
             }
-            nb = ceil_div(C.in.n_rays, kRayTile);
+            nb = ceil_div(C.inp.n_rays, kRayTile);
             break;
         }
         case EMER_RAY_JOB_BWD_CHAIN: {

@@ -21,41 +21,20 @@ import contextlib
 import functools
 import os
 import ctypes
-from ctypes import c_int32, c_int64, c_void_p
 from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _lib, ray_jobs
-from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP
+from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP, CONST, STRUCT, _ng, _stream  # noqa: F401
+from ._lib import _f32c as _c, _ptr as _p
 
-MAX_LAYERS, MAX_SEGS = 6, 3
+MAX_LAYERS, MAX_SEGS = CONST["EMER_CHAIN_MAX_LAYERS"], CONST["EMER_CHAIN_MAX_SEGS"]
 E15 = 3269017.3724721107
 
-
-class ChainSeg(ctypes.Structure):
-    _fields_ = [("ptr", c_void_p), ("ld", c_int64), ("n_total", c_int64), ("fix_a", c_void_p), ("fix_b", c_void_p),
-                ("col", c_int32), ("width", c_int32), ("row_div", c_int32), ("mode", c_int32), ("f", c_int32), ("dst_col", c_int32)]
-
-
-class ChainLayer(ctypes.Structure):
-    _fields_ = [("w", c_void_p), ("w_sn", c_int64), ("w_sk", c_int64), ("bias", c_void_p), ("mask", c_void_p),
-                ("mask_ld", c_int64), ("store", c_void_p), ("store_ld", c_int64), ("store_ntotal", c_int64),
-                ("store_exp0", c_void_p), ("in_col", c_int32), ("K", c_int32), ("out_col", c_int32), ("N", c_int32),
-                ("act", c_int32), ("accumulate", c_int32), ("store_col", c_int32), ("store_n", c_int32),
-                ("store_mode", c_int32), ("store_f", c_int32)]
-
-
-class ChainDesc(ctypes.Structure):
-    _fields_ = [("segs", ChainSeg * MAX_SEGS), ("layers", ChainLayer * MAX_LAYERS), ("n_segs", c_int32),
-                ("n_layers", c_int32), ("buf_cols", c_int32), ("_pad", c_int32)]
-
-
-class RayWgradJob(ctypes.Structure):
-    """emer_ray_wgrad_job of include/emernerf_hip.h."""
-    _fields_ = [("dy", c_void_p), ("ld_dy", c_int64), ("x", c_void_p * 2), ("ld_x", c_int64 * 2), ("dw", c_void_p), ("ld_dw", c_int64),
-                ("dbias", c_void_p), ("n", c_int32), ("n_segs", c_int32), ("width", c_int32 * 2), ("dst_col", c_int32 * 2)]
+ChainSeg, ChainLayer, ChainDesc = STRUCT["emer_chain_seg"], STRUCT["emer_chain_layer"], STRUCT["emer_chain_desc"]
+RayWgradJob = ray_jobs.WgradJob
 
 
 def ray_wgrad(jobs, ref: Tensor) -> None:
@@ -72,25 +51,6 @@ def ray_wgrad(jobs, ref: Tensor) -> None:
             a.x[i], a.ld_x[i], a.width[i], a.dst_col[i] = x.data_ptr(), x.stride(0), width, dst
     with torch.cuda.device(ref.device):
         _lib.call("emer_ray_wgrad", arr, len(jobs), M, _stream(ref))
-
-
-def _ng(*args):
-    """Arguments for a Function.apply call outside autograd recording (torch.no_grad, set_grad_enabled(False): evaluation,
-    the proposal sampling of the steps that do not train the proposal nets).  A Function's forward still sees
-    needs_input_grad == requires_grad of its inputs there (and torch.is_grad_enabled() is False inside EVERY forward), so
-    the inputs are detached here: the forwards then skip what only a backward needs -- hidden activations (256 B per sample),
-    the grid backward's bitmaps -- instead of writing it for nobody."""
-    if torch.is_grad_enabled():
-        return args
-    return tuple(a.detach() if isinstance(a, Tensor) else a for a in args)
-
-
-def _p(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(t: Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def seg(t: Tensor, col: int, width: int, ld: Optional[int] = None, row_div: int = 1, dst_col: Optional[int] = None) -> ChainSeg:
@@ -269,10 +229,6 @@ def _target(sink: Optional[Tensor], shape, dev):
 
 def _r4(x: int) -> int:
     return (x + 3) // 4 * 4
-
-
-def _c(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float32).contiguous()
 
 
 # ------------------------------------------------------------------------- row-buffer layouts of the chain heads

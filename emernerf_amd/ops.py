@@ -12,35 +12,15 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP, F16, F32, GridDesc, STOT_TYPES
+from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP, CONST, F16, F32, GridDesc, STOT_TYPES, STRUCT, _f32c, _ng, _ptr, _stream  # noqa: F401
 
 _ACTS = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "trunc_exp": ACT_TRUNC_EXP}
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(t: Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _check_cuda(*ts: Tensor):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise _lib.EmerError("emernerf_amd ops need GPU (HIP) tensors; there is no CPU fallback")
-
-
-def _ng(*args):
-    """Outside autograd recording the inputs of a Function.apply call are detached, so that its forward does not prepare a
-    backward nobody will run (see fused._ng)."""
-    if torch.is_grad_enabled():
-        return args
-    return tuple(a.detach() if isinstance(a, Tensor) else a for a in args)
-
-
-def _f32c(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float32).contiguous()
 
 
 def _opt(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -62,7 +42,7 @@ def _dtype_tag(t: Tensor) -> int:
 
 
 # ------------------------------------------------------------------------------------ hash grid
-MASK_SCRATCH = 2064  # EMER_SLICE_MASK_SCRATCH: work cursors (and pacing counters) of the backward behind the bitmaps
+MASK_SCRATCH = CONST["EMER_SLICE_MASK_SCRATCH"]  # work cursors (and pacing counters) of the backward behind the bitmaps
 
 
 def sliced_supported(desc: GridDesc) -> bool:
@@ -821,7 +801,7 @@ def pixel_loss(rgb: Tensor, opacity: Optional[Tensor], pixels: Tensor, sky_mask:
     return _PixelLossFn.apply(rgb, opacity, pixels, sky_mask, w_rgb, w_sky, grad_scale)
 
 
-REG_MAX_BLOCKS = 1024  # EMER_REG_MAX_BLOCKS
+REG_MAX_BLOCKS = CONST["EMER_REG_MAX_BLOCKS"]
 
 
 class _RegLossesFn(torch.autograd.Function):
@@ -1335,18 +1315,14 @@ def sq_err_sums(pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, out
 
 
 # ------------------------------------------------------------------------------------ order statistics (radix select)
-SELECT_JOBS_MAX = 16          # EMER_SELECT_JOBS_MAX
-SELECT_SOURCES_MAX = 4        # EMER_SELECT_SOURCES_MAX: distinct columns of one call
-SELECT_PER_SOURCE_MAX = 4     # EMER_SELECT_PER_SOURCE_MAX: distinct ranks / percentiles per column (a quantile takes two)
-SELECT_ROWS_MAX = 2 ** 31 - 1
+SELECT_JOBS_MAX = CONST["EMER_SELECT_JOBS_MAX"]
+SELECT_SOURCES_MAX = CONST["EMER_SELECT_SOURCES_MAX"]                # distinct columns of one call
+SELECT_PER_SOURCE_MAX = CONST["EMER_SELECT_PER_SOURCE_MAX"]          # distinct ranks / percentiles per column (a quantile takes two)
+SELECT_ROWS_MAX = CONST["EMER_SELECT_ROWS_MAX"]
 SELECT_VECTOR_ROWS = 1024     # rows that one workgroup takes per step on the 16-byte-load path (256 on the scalar path)
 SELECT_MAX_BLOCKS = 1024      # beyond it the workgroups stride over the rows
-_SEL_ORDER, _SEL_QUANTILE, _SEL_WPERCENT = 0, 1, 2
-
-
-class _SelectJob(ctypes.Structure):
-    """emer_select_job of include/emernerf_hip.h."""
-    _fields_ = [("column", ctypes.c_int32), ("output", ctypes.c_int32), ("param", ctypes.c_double), ("out", ctypes.c_void_p)]
+_SEL_ORDER, _SEL_QUANTILE, _SEL_WPERCENT = CONST["EMER_SELECT_ORDER"], CONST["EMER_SELECT_QUANTILE"], CONST["EMER_SELECT_WPERCENT"]
+_SelectJob = STRUCT["emer_select_job"]
 
 
 def _select(src: Tensor, n: int, stride: int, radius: bool, weights: Optional[Tensor], jobs, out_dtype) -> Tensor:
@@ -1373,7 +1349,7 @@ def _select(src: Tensor, n: int, stride: int, radius: bool, weights: Optional[Te
             arr = (_SelectJob * len(part))()
             for k, (i, col, output, param) in enumerate(part):
                 arr[k] = _SelectJob(int(col), output, float(param), out.data_ptr() + i * item)
-            _lib.call("emer_select", _ptr(src), 1 if radius else 0, stride, _ptr(weights), arr, len(part), n, _ptr(ws), _stream(src))
+            _lib.call("emer_select", _ptr(src), CONST["EMER_SELECT_RADIUS" if radius else "EMER_SELECT_COLUMNS"], stride, _ptr(weights), arr, len(part), n, _ptr(ws), _stream(src))
     return out
 
 
@@ -1457,7 +1433,7 @@ def weighted_percentile(x: Tensor, w: Tensor, ps) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------ evaluation colours
-COLOUR_JOBS_MAX = 8
+COLOUR_JOBS_MAX = CONST["EMER_COLOUR_JOBS_MAX"]
 _TRANSITIONS = (15, 6, 4, 11, 13, 6)
 _WHEELS: dict = {}
 
@@ -1483,19 +1459,7 @@ def _wheel_on(device) -> Tensor:
     return w
 
 
-class _FeatJob(ctypes.Structure):
-    """emer_feature_colour_job of include/emernerf_hip.h."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("feat", "mat", "lo", "hi", "scale", "out")]
-
-
-class _BlendJob(ctypes.Structure):
-    """emer_blend_over_job."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("a", "o", "b", "out")]
-
-
-class _FlowJob(ctypes.Structure):
-    """emer_flow_colour_job."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("flow", "out")]
+_FeatJob, _BlendJob, _FlowJob = STRUCT["emer_feature_colour_job"], STRUCT["emer_blend_over_job"], STRUCT["emer_flow_colour_job"]
 
 
 def _rows(t: Tensor, cols: int, what: str) -> Tensor:
@@ -1632,15 +1596,10 @@ def flow_colours(flow: Tensor, max_radius=1.0, background: str = "bright") -> Te
 
 
 # ------------------------------------------------------------------------------------ video frames (8-bit, merged)
-FRAME_TILES_MAX = 48     # EMER_FRAME_TILES_MAX
-TILE_KINDS = {"colour3": 0, "grey1": 1, "one_minus_grey1": 2, "depth": 3}   # EMER_TILE_*
+FRAME_TILES_MAX = CONST["EMER_FRAME_TILES_MAX"]
+TILE_KINDS = {k: CONST["EMER_TILE_" + k.upper()] for k in ("colour3", "grey1", "one_minus_grey1", "depth")}
+_FrameTile = STRUCT["emer_frame_tile"]
 _TURBO8: dict = {}
-
-
-class _FrameTile(ctypes.Structure):
-    """emer_frame_tile of include/emernerf_hip.h."""
-    _fields_ = [("src", ctypes.c_void_p), ("opacity", ctypes.c_void_p), ("kind", ctypes.c_int32), ("row", ctypes.c_int32),
-                ("col", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def turbo_table():
@@ -1753,16 +1712,10 @@ def depth_colours(depth: Tensor, opacity: Tensor, lo=4.0, hi=120.0) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------ voxel lift (bit masks)
-VOXEL_JOBS_MAX = 4
-MEAN_ARRAYS_MAX = 8
-BITS_ROW_COLS_MAX = 4
-
-
-class _VoxelMarkJob(ctypes.Structure):
-    """emer_voxel_mark_job of include/emernerf_hip.h."""
-    _fields_ = [("origins", ctypes.c_void_p), ("viewdirs", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("bits", ctypes.c_void_p),
-                ("max_depth", ctypes.c_float), ("aabb_min", ctypes.c_float * 3), ("voxel_size", ctypes.c_float * 3),
-                ("res", ctypes.c_int32 * 3)]
+VOXEL_JOBS_MAX, VOXELS_MAX = CONST["EMER_VOXEL_JOBS_MAX"], CONST["EMER_VOXELS_MAX"]
+MEAN_ARRAYS_MAX = CONST["EMER_MEAN_ARRAYS_MAX"]
+BITS_ROW_COLS_MAX = CONST["EMER_BITS_ROW_COLS_MAX"]
+_VoxelMarkJob = STRUCT["emer_voxel_mark_job"]
 
 
 def bit_words(n_bits: int) -> int:
@@ -1786,7 +1739,7 @@ def _triple(v, kind, what: str):
 
 
 def _voxel_count(res, what: str) -> int:
-    if any(r < 1 or r >= 1 << 24 for r in res) or res[0] * res[1] * res[2] > 2 ** 31 - 1:
+    if any(r < 1 or r >= 1 << 24 for r in res) or res[0] * res[1] * res[2] > VOXELS_MAX:
         raise _lib.EmerError(f"{what}: resolution {res}: every axis in 1 .. 2^24 - 1 and at most 2^31 - 1 voxels")
     return res[0] * res[1] * res[2]
 

@@ -7,7 +7,7 @@ workgroup per table row) cost 62 us as three launches and 27 us as one; the row-
 gain little (in two sessions: front 36.7 / 28.9 us against 37.8 / 37.4 us as four launches, launch A 42.0 / 35.2 us against
 43.3 / 43.5 us): for them the job launch mostly saves launches.  This module holds
 
-  * the ctypes mirror of ``emer_ray_job`` and builders for the job kinds,
+  * ``emer_ray_job`` and its argument structs (read from the header) and builders for the job kinds,
   * the FRONT launch's parking place: results computed ahead of the Functions that own them (``Front``), picked up by
     identity checks only, exactly like ``fused.RgbRider``,
   * the per-step QUEUE of deferred backward jobs: level A (row-local chains, the reduction of the rgb backward's partials)
@@ -24,94 +24,26 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from ctypes import c_int32, c_int64, c_void_p
 from typing import List, Optional
 
 import torch
 from torch import Tensor
 
 from . import _lib
+from ._lib import CONST, STRUCT, _ptr as _p, _stream
 
 # the switch: EMER_RAY_JOBS=0 (or ENABLED = False) gives the separate launches exactly
 ENABLED = os.environ.get("EMER_RAY_JOBS", "1") != "0"
 
-MAX_JOBS = 8
-INPUTS, PRE_FWD, HEAD_FWD, HEAD_BWD, PRE_BWD, WGRAD, EMBED_GRAD, DW_REDUCE, FWD_CHAIN, BWD_CHAIN = range(1, 11)
+MAX_JOBS = CONST["EMER_RAY_JOBS_MAX"]
+INPUTS, PRE_FWD, HEAD_FWD, HEAD_BWD, PRE_BWD, WGRAD, EMBED_GRAD, DW_REDUCE, FWD_CHAIN, BWD_CHAIN = (
+    CONST["EMER_RAY_JOB_" + k] for k in ("INPUTS", "PRE_FWD", "HEAD_FWD", "HEAD_BWD", "PRE_BWD", "WGRAD", "EMBED_GRAD", "DW_REDUCE",
+                                        "FWD_CHAIN", "BWD_CHAIN"))
 
-_P = c_void_p
-
-
-class InputsArgs(ctypes.Structure):
-    _fields_ = [("dirs", _P), ("ld_dirs", c_int64), ("idx", _P), ("idx_stride", c_int64), ("emb", _P), ("n_emb", c_int32),
-                ("emb_dim", c_int32), ("max_deg", c_int32), ("pad_", c_int32), ("n_rays", c_int64), ("out_rgb", _P), ("ld_rgb", c_int64),
-                ("out_sky", _P), ("ld_sky", c_int64)]
-
-
-class PreFwdArgs(ctypes.Structure):
-    _fields_ = [("h", _P), ("ld_h", c_int64), ("n_rays", c_int64), ("kh", c_int32), ("n_hidden", c_int32), ("wa", _P), ("ld_wa", c_int64),
-                ("ba", _P), ("wb", _P), ("ld_wb", c_int64), ("bb", _P), ("rb", _P), ("ld_rb", c_int64)]
-
-
-class PreBwdArgs(ctypes.Structure):
-    _fields_ = [("s0", _P), ("s1", _P), ("ld_s", c_int64), ("n_rays", c_int64), ("kh", c_int32), ("n_hidden", c_int32), ("wa", _P),
-                ("ld_wa", c_int64), ("wb", _P), ("ld_wb", c_int64), ("dh", _P), ("ld_dh", c_int64)]
-
-
-class HeadFwdArgs(ctypes.Structure):
-    _fields_ = [("rb", _P), ("ld_rb", c_int64), ("n_rows", c_int64), ("w1", _P), ("ld_w1", c_int64), ("w2", _P), ("b2", _P),
-                ("n_out", c_int32), ("act", c_int32), ("a1", _P), ("a2", _P), ("out", _P)]
-
-
-class HeadBwdArgs(ctypes.Structure):
-    _fields_ = [("dout", _P), ("out", _P), ("a1", _P), ("a2", _P), ("n_rows", c_int64), ("w1", _P), ("ld_w1", c_int64), ("w2", _P),
-                ("n_out", c_int32), ("act", c_int32), ("dpre2", _P), ("dpre1", _P), ("dpre0", _P)]
-
-
-class EmbedGradArgs(ctypes.Structure):
-    _fields_ = [("g_a", _P), ("ld_a", c_int64), ("g_b", _P), ("ld_b", c_int64), ("idx", _P), ("idx_stride", c_int64), ("n_rays", c_int64),
-                ("n_emb", c_int32), ("emb_dim", c_int32), ("dw", _P)]
-
-
-class WgradJob(ctypes.Structure):
-    """emer_ray_wgrad_job of include/emernerf_hip.h."""
-    _fields_ = [("dy", _P), ("ld_dy", c_int64), ("x", _P * 2), ("ld_x", c_int64 * 2), ("dw", _P), ("ld_dw", c_int64),
-                ("dbias", _P), ("n", c_int32), ("n_segs", c_int32), ("width", c_int32 * 2), ("dst_col", c_int32 * 2)]
-
-
-class WgradArgs(ctypes.Structure):
-    _fields_ = [("job", WgradJob), ("m", c_int64)]
-
-
-class DwReduceJob(ctypes.Structure):
-    _fields_ = [("off", c_int64), ("n", c_int32), ("k", c_int32), ("dw", _P), ("ld_dw", c_int64), ("db", _P), ("n_segs", c_int32),
-                ("col", c_int32 * 4), ("width", c_int32 * 4), ("dst", c_int32 * 4), ("pad_", c_int32)]
-
-
-class DwReduceArgs(ctypes.Structure):
-    _fields_ = [("partials", _P), ("stride", c_int64), ("n_blocks", c_int32), ("n_jobs", c_int32), ("job", DwReduceJob * 3)]
-
-
-class _FwdChain(ctypes.Structure):
-    _fields_ = [("inp", InputsArgs), ("pre", PreFwdArgs), ("head", HeadFwdArgs)]
-
-
-class _BwdChain(ctypes.Structure):
-    _fields_ = [("head", HeadBwdArgs), ("pre", PreBwdArgs)]
-
-
-class _JobU(ctypes.Union):
-    _fields_ = [("inputs", InputsArgs), ("pre_fwd", PreFwdArgs), ("head_fwd", HeadFwdArgs), ("head_bwd", HeadBwdArgs), ("pre_bwd", PreBwdArgs),
-                ("wgrad", WgradArgs), ("embed_grad", EmbedGradArgs), ("dw_reduce", DwReduceArgs), ("fwd_chain", _FwdChain),
-                ("bwd_chain", _BwdChain)]
-
-
-class RayJob(ctypes.Structure):
-    """emer_ray_job of include/emernerf_hip.h."""
-    _fields_ = [("kind", c_int32), ("n_stages", c_int32), ("u", _JobU)]
-
-
-def _p(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
+# emer_ray_job and the argument structs of its kinds (include/emernerf_hip.h)
+InputsArgs, PreFwdArgs, PreBwdArgs, HeadFwdArgs, HeadBwdArgs, EmbedGradArgs, WgradJob, WgradArgs, DwReduceJob, DwReduceArgs, RayJob = (
+    STRUCT["emer_" + k] for k in ("ray_inputs_args", "ray_pre_fwd_args", "ray_pre_bwd_args", "ray_head_fwd_args", "ray_head_bwd_args",
+                                  "embed_grad_args", "ray_wgrad_job", "ray_wgrad_args", "dw_reduce_job", "dw_reduce_args", "ray_job"))
 
 
 # ------------------------------------------------------------------------------------------------ builders
@@ -194,7 +126,7 @@ def launch(jobs: List[RayJob], ref: Tensor) -> None:
     """The jobs in as few launches as EMER_RAY_JOBS_MAX allows (one, for every list this package builds), on ``ref``'s device and
     torch's current stream."""
     with torch.cuda.device(ref.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)
+        stream = _stream(ref)
         for i in range(0, len(jobs), MAX_JOBS):
             part = jobs[i:i + MAX_JOBS]
             arr = (RayJob * len(part))(*part)

@@ -707,7 +707,7 @@ int emer_ray_wgrad(const emer_ray_wgrad_job *jobs, int32_t n_jobs, int64_t m, vo
  *   FWD_CHAIN  emer_ray_inputs_fwd -> emer_ray_pre_fwd [-> emer_ray_head_fwd]   (n_stages 2 or 3)
  *   BWD_CHAIN  emer_ray_head_bwd -> emer_ray_pre_bwd
  * Every stage of a chain still writes its outputs to memory exactly as the separate launch does; the caller wires the stages up
- * through the pointers (e.g. pre.h == in.out_sky, head.rb == pre.rb), all stages of a chain share the row count.
+ * through the pointers (e.g. pre.h == inp.out_sky, head.rb == pre.rb), all stages of a chain share the row count.
  * DW_REDUCE is the reduction of a fused backward kernel's per-workgroup partials, as captured by emer_dw_reduce_defer. */
 #define EMER_RAY_JOBS_MAX 8
 #define EMER_RAY_JOB_INPUTS 1
@@ -765,7 +765,7 @@ typedef struct emer_ray_job {
         emer_ray_wgrad_args wgrad;
         emer_embed_grad_args embed_grad;
         emer_dw_reduce_args dw_reduce;
-        struct { emer_ray_inputs_args in; emer_ray_pre_fwd_args pre; emer_ray_head_fwd_args head; } fwd_chain;
+        struct { emer_ray_inputs_args inp; emer_ray_pre_fwd_args pre; emer_ray_head_fwd_args head; } fwd_chain;
         struct { emer_ray_head_bwd_args head; emer_ray_pre_bwd_args pre; } bwd_chain;
     } u;
 } emer_ray_job;

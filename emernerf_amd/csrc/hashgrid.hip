@@ -1308,12 +1308,24 @@ __global__ __launch_bounds__(kSliceThreads) void hashgrid_bwd_params_sliced_kern
             if constexpr (dense) {
                 // ---- run-segmented reduction: lanes with the same cell as their predecessor join its run
                 uint32_t cell = 0, mul = 1;
+                bool outside = false;
 #pragma unroll
-                for (int d = 0; d < D; ++d) { cell += gi[d] * mul; mul *= li.res + 1u; }
+                for (int d = 0; d < D; ++d) { cell += gi[d] * mul; mul *= li.res + 1u; outside |= gi[d] > li.res; }
                 if (!valid) cell = 0xFFFFFFFFu;
                 // (head / RunMasks / next_head: twin of add_pair_runs')
                 const uint32_t prev = wave_prev_u32(cell, ~cell);
-                const bool head = cell != prev;  // (lane 0 compares with ~cell: always a head)
+                bool head = cell != prev;  // (lane 0 compares with ~cell: always a head)
+                // The packed key tells cells apart only while every gi[d] <= res, which coordinates in [0, 1] guarantee.  Coordinates
+                // outside wrap (tcnn semantics) and two DIFFERENT neighbouring cells may then share a key -- (res + 1, y) and (0, y + 1) --
+                // and would be summed into one run: a wave holding such a hit compares the coordinates one by one (wave-uniform test,
+                // never taken by EmerNeRF's own inputs; invalid lanes are runs of their own).
+                if (__ballot(valid && outside)) {
+                    const uint32_t vkey = valid ? 0u : 1u + (uint32_t)lane;
+                    uint32_t diff = vkey ^ wave_prev_u32(vkey, ~vkey);
+#pragma unroll
+                    for (int d = 0; d < D; ++d) diff |= gi[d] ^ wave_prev_u32(gi[d], ~gi[d]);
+                    head = diff != 0u;
+                }
                 const RunMasks rm = run_masks(head);
                 const bool next_head = wave_next_u32(head ? 1u : 0u, 1u) != 0u;
                 const bool tail = valid && (lane == 63 || next_head);

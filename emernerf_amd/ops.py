@@ -187,6 +187,13 @@ def _table_grad_via_autograd(param, grad):
     return grad
 
 
+def _fp32_accumulation(gdt, desc: GridDesc) -> bool:
+    """The table gradient is summed in fp32: asked for, or half gradients of an ODD feature count (every proposal network has one
+    feature per level) -- the packed half2 atomics of emer_hashgrid_bwd_params need an even one, so such a gradient takes the fp32
+    routes (owner computes where the grid allows, else fp32 atomics) and is rounded to half once."""
+    return gdt == torch.float32 or bool(desc.n_features & 1)
+
+
 class _HashGridFn(torch.autograd.Function):
     """tcnn ``_module_function`` (third_party/tcnn_modules.py:115-174) on HIP.
 
@@ -200,7 +207,7 @@ class _HashGridFn(torch.autograd.Function):
         N, L, F = xc.shape[0], desc.n_levels, desc.n_features
         gdt = grad_dtype or torch.float32
         # the forward emits the slice masks of the owner-computes backward when it will be used
-        ctx.sliced = bool(ctx.needs_input_grad[1] and gdt == torch.float32 and sliced_supported(desc))
+        ctx.sliced = bool(ctx.needs_input_grad[1] and _fp32_accumulation(gdt, desc) and sliced_supported(desc))
         if ctx.sliced:
             lm, masks = hashgrid_fwd_raw(desc, xc, pc, level_major=True, want_masks=True)
         else:
@@ -224,15 +231,17 @@ class _HashGridFn(torch.autograd.Function):
             st = _stream(xc)
             if ctx.needs_input_grad[1]:
                 gdt = ctx.grad_dtype or torch.float32
-                if gdt == torch.float32 and masks is not None:
+                if masks is not None:
                     # owner-computes LDS scatter: writes every entry once (no memset, no global atomics)
                     grad = torch.empty(pc.numel(), device=xc.device, dtype=torch.float32)
                     _lib.call("emer_hashgrid_bwd_params_sliced", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks),
                               _ptr(grad), N, st)
                 else:  # tcnn-style global atomics: fp16-gradient mode, or tables too large for 32 LDS slices
-                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=gdt)
+                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=torch.float32 if _fp32_accumulation(gdt, desc) else gdt)
                     _lib.call("emer_hashgrid_bwd_params", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(grad),
                               _dtype_tag(grad), N, st)
+                if grad.dtype != gdt:
+                    grad = grad.to(gdt)  # (half gradients of an odd feature count: summed in fp32, rounded once)
                 dp = _table_grad_via_autograd(ctx.param_obj, grad.to(pc.dtype) if grad.dtype != pc.dtype else grad)
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(xc)
@@ -296,7 +305,7 @@ class _HashGridLMFn(torch.autograd.Function):
                 _lib.call("emer_cast_f32_f16", _ptr(pc), _ptr(ph), pc.numel(), _stream(pc))
             pc = ph  # what the kernels read; `params` stays the fp32 master (gradient sink)
         gdt = grad_dtype or torch.float32
-        ctx.sliced = bool(ctx.needs_input_grad[1] and gdt == torch.float32 and sliced_supported(desc))
+        ctx.sliced = bool(ctx.needs_input_grad[1] and _fp32_accumulation(gdt, desc) and sliced_supported(desc))
         k = min(int(skip_dx_rows), xc.shape[0])
         jac = None
         if GRID_JAC and ctx.needs_input_grad[0] and pc.dtype == torch.float32 and k < xc.shape[0] and _jac_fits(desc, xc.shape[0] - k):
@@ -311,7 +320,7 @@ class _HashGridLMFn(torch.autograd.Function):
         ctx.skip_dx_rows = int(skip_dx_rows)
         ctx.master_dtype = params.dtype
         from . import fused
-        sink = fused._sink(params) if ctx.sliced else None
+        sink = fused._sink(params) if (ctx.sliced and gdt == torch.float32) else None
         ctx.param = params if (sink is not None and sink.is_contiguous() and sink.numel() == pc.numel()) else None
         ctx.param_obj = params
         _count_table_eval(params)
@@ -332,7 +341,7 @@ class _HashGridLMFn(torch.autograd.Function):
             st = _stream(xc)
             if ctx.needs_input_grad[1]:
                 gdt = ctx.grad_dtype or torch.float32
-                if gdt == torch.float32 and masks is not None:
+                if masks is not None:
                     param = ctx.param
                     direct = param is not None and getattr(param, "_emer_grad_fresh", False) and param.grad is not None
                     # [r5] a further evaluation of the same encoder in this step adds to the table's buffer in the kernel's write-out
@@ -362,9 +371,11 @@ class _HashGridLMFn(torch.autograd.Function):
                         param.grad.view(-1).add_(grad)  # a further evaluation of the same encoder in this step
                         grad = None
                 else:
-                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=gdt)
+                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=torch.float32 if _fp32_accumulation(gdt, desc) else gdt)
                     _lib.call("emer_hashgrid_bwd_params", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(grad),
                               _dtype_tag(grad), N, st)
+                if grad is not None and grad.dtype != gdt:
+                    grad = grad.to(gdt)  # (half gradients of an odd feature count: summed in fp32, rounded once)
                 dp = None if grad is None else _table_grad_via_autograd(ctx.param_obj, grad.to(ctx.master_dtype) if grad.dtype != ctx.master_dtype else grad)
                 _after_table_grad(ctx.param_obj, last, dp is None)
             if ctx.needs_input_grad[0]:

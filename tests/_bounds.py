@@ -84,6 +84,57 @@ def c_sliced(meta, desc, hits: np.ndarray, accumulate: bool = False) -> np.ndarr
     return c
 
 
+# fp16 gradient tables: hashgrid_bwd_params_kernel<D, F, __half> (emer_hashgrid_bwd_params with EMER_F16, packed half2 atomics).
+# A term wt * go is formed in fp32 (2D roundings at u = 2^-24), converted to half (one rounding at u16 = 2^-11) and added to the
+# entry by one of `hits` half atomics in arbitrary order; every addition rounds a partial sum to half.  By the usual induction
+# (every term passes its conversion and at most `hits` additions; partial sums of the rounded terms included) the relative
+# part is
+#
+#     |got - ref| <= ((1 + 2D u) (1 + gamma_k) - 1) abs_sum,   gamma_k = k u16 / (1 - k u16),   k = hits + 1 (+ extra)
+#
+# which needs k u16 < 1 (asserted: fewer than 2047 hits).  ``extra``: further half roundings the value passes on the route
+# under test (a cast of the finished gradient).  The absolute part, (hits + 1) 2^-14 per entry, is for results below the normal
+# half range (2^-14): whether the packed half atomic of this device keeps or flushes them has not been measured; a kept
+# subnormal is off by at most 2^-25 per operation, a flushed one by less than 2^-14, and the term allows one such loss per
+# addition and one for the value read back.  The bound is meant for gradients of order 1 - 10 (what loss scale 128 produces),
+# where the relative part dominates; the exact probes of tests/test_hashgrid_instances_gpu.py do not depend on it.  Half sums
+# overflow at 65504: asserted here from abs_sum (every partial sum is at most (1 + gamma_k) abs_sum).
+#
+# Measured worst err / bound on an MI355X (tests/test_hashgrid_instances_gpu.py; the atomic order varies from run to run):
+#   half atomics, n = 4099, |dOut| in [1, 10], the even-F grids of GRIDS (fp16_atomic_bound)        0.635 (cfg2_static)
+#   Encoding(dtype=float16).forward, even F, n = 1000 (fp16_atomic_bound, extra = 1)                 0.427 (D = 4, F = 4)
+#   half gradients of an odd feature count, n = 1000 (c_sliced, half_rounded_bound)                  0.996 (the one half rounding:
+#       its error reaches 2^-11 of the value at the bottom of a binade, so this ratio sits just below 1 by construction)
+#   fp32 atomics, n = 4099, every grid of GRIDS, both dOut layouts (c_atomic)                        0.302 (dynamic_xyzt)
+#   gather input gradient with an fp16 table, n = 4099, every grid of GRIDS (c_input_grad)           0.197 (tiny_2d_f1)
+#   hashgrid_encode_lm(table_dtype=float16, skip_dx_rows): input gradient (c_input_grad) 0.050, master gradient (c_sliced) 0.211
+U16 = 2.0 ** -11
+HALF_MIN_NORMAL = 2.0 ** -14
+HALF_MAX = 65504.0
+
+
+def fp16_atomic_bound(D: int, hits: np.ndarray, abs_sum: np.ndarray, extra: int = 0) -> np.ndarray:
+    """Per table VALUE (entry, feature) error bound of the half-atomic backward, as an absolute error (see above);
+    0 where abs_sum is 0: such an entry must come out exactly 0."""
+    hits = np.asarray(hits, np.float64)
+    abs_sum = np.asarray(abs_sum, np.float64).reshape(-1)
+    F = abs_sum.size // hits.size
+    assert F * hits.size == abs_sum.size
+    k = np.repeat(hits, F) + 1.0 + extra
+    assert float(k.max()) * U16 < 1.0, f"gamma_k needs k u < 1: {int(k.max())} roundings at u = 2^-11"
+    gamma = k * U16 / (1.0 - k * U16)
+    assert float(((1.0 + gamma) * abs_sum).max()) <= HALF_MAX, "a half partial sum may overflow"
+    rel = (1.0 + 2 * D * U) * (1.0 + gamma) - 1.0
+    return np.where(abs_sum > 0, rel * abs_sum + (np.repeat(hits, F) + 1.0) * HALF_MIN_NORMAL, 0.0)
+
+
+def half_rounded_bound(err: np.ndarray, ref: np.ndarray) -> np.ndarray:
+    """A value within ``err`` of ``ref`` that is then rounded to half once (round to nearest, subnormals kept: torch's
+    cast): u16 of the value before the cast, or half a subnormal step (2^-25); 0 stays 0."""
+    err, ref = np.asarray(err, np.float64), np.abs(np.asarray(ref, np.float64))
+    return np.where(err > 0, err + np.maximum(U16 * (ref + err), 2.0 ** -25), 0.0)
+
+
 # ---------------------------------------------------------------------------------------------------------- assertion
 def _level_of_entry(meta, e: int) -> int:
     return int(np.searchsorted(meta.offset.astype(np.int64), e, side="right") - 1)

@@ -24,6 +24,13 @@ GRIDS = {
     "cfg0_static": (3, 4, 16, 2048, 19, 2),        # BASELINE configs[0]: fewer levels than XCDs; level 1 (res 81) barely hashed
     "tiny_f8": (3, 4, 4, 64, 10, 8),
     "tiny_2d": (2, 5, 8, 256, 12, 2),
+    # the (D, F) instantiations of dispatch_df that no grid above reaches
+    "tiny_2d_f1": (2, 5, 8, 256, 12, 1),
+    "tiny_2d_f4": (2, 5, 8, 256, 12, 4),
+    "tiny_2d_f8": (2, 5, 8, 256, 12, 8),
+    "tiny_4d_f1": (4, 4, 4, 32, 12, 1),            # level 0 (5^4 cells) is dense: the xyzt tables above are hashed from level 0
+    "tiny_4d_f2": (4, 4, 4, 32, 12, 2),
+    "tiny_4d_f8": (4, 4, 4, 32, 12, 8),
 }
 
 

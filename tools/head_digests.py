@@ -1,8 +1,14 @@
-"""SHA-256 digests of what the heads with register-resident weight gradients compute (emer_rgb_head_bwd_fused, emer_rgb_head_bwd_recompute,
-emer_neck_bwd_fused, emer_rmlp_bwd_fused, reached through emernerf_amd.fused) on seeded CPU-generated inputs, and with --time the device-event
-medians of their backward at the metric shapes.  Run once per library and compare: a refactor of those kernels must leave every digest as it was.
+"""SHA-256 digests of what the fused heads compute through emernerf_amd.fused on seeded CPU-generated inputs: the heads with
+register-resident weight gradients at their probe shapes (emer_rgb_head_bwd_fused, emer_rgb_head_bwd_recompute, emer_neck_bwd_fused,
+emer_rmlp_bwd_fused) and EVERY path of the path table of fused.py (tests/_fused_paths.py: the flag matrix, density_mlp, base_mlp, skip_mlp3,
+the chain shapes); with --launches the library calls and the device kernels of each path, with --time the device-event medians of the
+fused backwards at the metric shapes.  Run once per library or per checkout and compare: a refactor of those kernels, or of the Python
+that chooses among them, must leave every digest and every list as it was.
 
-usage: python tools/head_digests.py [--lib tag] [--time] [--out file.json]
+usage: python tools/head_digests.py [--tree DIR] [--lib tag] [--launches] [--time] [--out file.json]
+
+--tree DIR imports emernerf_amd from another checkout (the parent commit in a git worktree, with its library built); the cases are
+this checkout's either way.
 
 Digested: the outputs and data gradients at every shape; the weight and bias gradients only where their final reduction meets in no float
 atomic (at most 16 rays / 128 rows: one workgroup range), as tests/test_fused_gpu.py documents for the bitwise test."""
@@ -13,7 +19,15 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tests import _fused_paths as T  # noqa: E402  (imports no emernerf_amd)
+TREE = ROOT
+if "--tree" in sys.argv:
+    i = sys.argv.index("--tree")
+    TREE = os.path.abspath(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    sys.path.insert(0, TREE)
 from tools import _libsel  # noqa: E402
 from emernerf_amd import fused, _lib  # noqa: E402
 from tools.kbench import timeit  # noqa: E402
@@ -91,6 +105,15 @@ def rmlp_case(dims, N, lm=None):
     return d
 
 
+def path_case(case_id):
+    outs, leaves = T.run_case(case_id, DEV)
+    d = {f"out{i}": sha(o) for i, o in enumerate(outs)}
+    rows = T.CASES[case_id][3][1]
+    few = rows <= (16 if case_id.startswith("rgb") else 128)
+    d.update({f"d{i}": sha(t.grad) for i, t in enumerate(leaves) if i < (2 if case_id.startswith("rgb") else 1) or few})
+    return d
+
+
 def digests():
     res = {}
     for R, S, Kh, ld in RGB:
@@ -103,6 +126,31 @@ def digests():
         res[f"rmlp {dims} N{N}"] = rmlp_case(dims, N)
     for L, F, dims, N in RMLP_LM:
         res[f"rmlp_lm L{L} F{F} {dims} N{N}"] = rmlp_case(dims, N, lm=(L, F))
+    for case_id in T.CASES:
+        res["path " + case_id] = path_case(case_id)
+    return res
+
+
+def launches():
+    """Per path: the names passed to _lib.call (forward, T.BACKWARD, backward) and the ordered device kernels of forward + backward from
+    one torch.profiler run (torch's own elementwise and fill kernels included; copies and memsets are no kernels)."""
+    from torch.profiler import ProfilerActivity, profile
+    res = {}
+    real = _lib.call
+    for case_id in T.CASES:
+        names = []
+        _lib.call = lambda name, *a: (names.append(name), real(name, *a))[1]
+        try:
+            T.run_case(case_id, DEV, names)
+        finally:
+            _lib.call = real
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            T.run_case(case_id, DEV)
+            torch.cuda.synchronize()
+        kernels = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and e.device_time_total > 0]
+        kernels = [e.name for e in sorted(kernels, key=lambda e: e.time_range.start)]
+        res[case_id] = {"calls": names, "kernels": [k for k in kernels if "Memcpy" not in k and "Memset" not in k]}
     return res
 
 
@@ -151,7 +199,9 @@ def main():
         i = sys.argv.index("--out")
         out_path = sys.argv[i + 1]
         del sys.argv[i:i + 2]
-    res = {"lib": _libsel.TAG, "digests": digests()}
+    res = {"lib": _libsel.TAG, "tree": os.path.relpath(TREE, ROOT), "digests": digests()}
+    if "--launches" in sys.argv:
+        res["launches"] = launches()
     if "--time" in sys.argv:
         res["median_us"] = timings()
     torch.cuda.synchronize()

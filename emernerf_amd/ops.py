@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, table_grad
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TRUNC_EXP, CONST, F16, F32, GridDesc, STOT_TYPES, STRUCT, _f32c, _ng, _ptr, _stream  # noqa: F401
 
 _ACTS = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "trunc_exp": ACT_TRUNC_EXP}
@@ -174,24 +174,79 @@ def _check_finite_grid_grad(dlm: Tensor, desc: GridDesc) -> None:
                                  f"(level, sample) {idx}{' ...' if int(bad.any(dim=-1).sum()) > 8 else ''}")
 
 
-def _table_grad_via_autograd(param, grad):
-    """A table gradient that is handed BACK to autograd (AccumulateGrad will add it onto ``param.grad``).  A trainer that
-    skips zeroing table gradients (``FlatParams.zero_grad`` marks them ``_emer_grad_fresh`` instead: the owner-computes
-    backward overwrites them) leaves last step's values in ``.grad``; every path that does not overwrite must therefore zero
-    the stale buffer first and clear the mark -- otherwise AccumulateGrad adds onto stale data and ``finish_grads`` later zeroes
-    the sum (the row-major / atomic / fp16 fallbacks trained with a zero gradient)."""
-    if grad is not None and param is not None and getattr(param, "_emer_grad_fresh", False):
-        if param.grad is not None:
-            param.grad.zero_()
-        param._emer_grad_fresh = False
-    return grad
-
-
 def _fp32_accumulation(gdt, desc: GridDesc) -> bool:
     """The table gradient is summed in fp32: asked for, or half gradients of an ODD feature count (every proposal network has one
     feature per level) -- the packed half2 atomics of emer_hashgrid_bwd_params need an even one, so such a gradient takes the fp32
     routes (owner computes where the grid allows, else fp32 atomics) and is rounded to half once."""
     return gdt == torch.float32 or bool(desc.n_features & 1)
+
+
+def _grid_forward(ctx, xc: Tensor, pc: Tensor, params: Tensor, desc: GridDesc, grad_dtype, jac_row0=None, sink_of=None):
+    """What the forwards of both grid Functions share -> (level-major encoding [L, N, F], Jacobian or None).  ``pc``: the table the
+    kernels read, ``params``: the parameter its gradient belongs to.  ``sink_of``: ``fused._sink`` if the table gradient may be written
+    straight into ``params.grad`` (asked, and recorded as ``ctx.param``, where the owner-computes backward will run in fp32)."""
+    gdt = grad_dtype or torch.float32
+    # the forward emits the slice masks of the owner-computes backward when it will be used
+    ctx.sliced = bool(ctx.needs_input_grad[1] and _fp32_accumulation(gdt, desc) and sliced_supported(desc))
+    res = hashgrid_fwd_raw(desc, xc, pc, level_major=True, want_masks=ctx.sliced, jac_row0=jac_row0)
+    res = res if isinstance(res, tuple) else (res,)
+    masks = res[1] if ctx.sliced else None
+    ctx.desc, ctx.grad_dtype, ctx.master_dtype = desc, grad_dtype, params.dtype
+    sink = sink_of(params) if (sink_of is not None and ctx.sliced and gdt == torch.float32) else None
+    ctx.param = params if (sink is not None and sink.is_contiguous() and sink.numel() == pc.numel()) else None
+    ctx.param_obj, ctx.table_route = params, None
+    table_grad.of(params).count_eval()
+    ctx.save_for_backward(xc, pc, masks)
+    return res[0], (res[-1] if jac_row0 is not None else None)
+
+
+def _enter_grid_backward(ctx, masks) -> None:
+    """First thing in both backwards, before any launch: the table's evaluation count (a data-parallel trainer's early bucket
+    fires on the table's last backward of the step) and the route of the table gradient (table_grad.route), once."""
+    state = table_grad.of(ctx.param_obj)
+    ctx.last = state.enter_backward()
+    if ctx.needs_input_grad[1]:
+        g = None if ctx.param is None else ctx.param.grad
+        # (the cut is taken only by the table's LAST backward of the step: an earlier one would start the collective of a range
+        # that a later backward of the same table still adds to)
+        k = state.split[0] if (ctx.last and state.split is not None) else 0
+        ctx.table_route = table_grad.route(sliced=masks is not None, sink=ctx.param is not None, has_grad=g is not None, fresh=state.fresh,
+                                           contiguous=g is not None and g.is_contiguous(), last_and_split=0 < k < ctx.desc.n_levels)
+
+
+def _table_gradient(ctx, desc: GridDesc, xc: Tensor, dlm: Tensor, masks, pc: Tensor, st):
+    """Run ``ctx.table_route`` (level-major ``dlm``) -> the gradient to hand back to autograd, None where it went into ``.grad``."""
+    N, L, F = xc.shape[0], desc.n_levels, desc.n_features
+    route, param, state = ctx.table_route, ctx.param, table_grad.of(ctx.param_obj)
+    gdt = ctx.grad_dtype or torch.float32
+    grad = None
+    if route == "atomic":  # tcnn-style global atomics: fp16-gradient mode, or tables too large for the LDS slices
+        grad = torch.zeros(pc.numel(), device=xc.device, dtype=torch.float32 if _fp32_accumulation(gdt, desc) else gdt)
+        _lib.call("emer_hashgrid_bwd_params", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(grad), _dtype_tag(grad), N, st)
+    elif route == "direct_split":
+        # data-parallel trainer: the levels [k, L) first, then ITS hook (the collective of that contiguous range of the table starts
+        # on the communication stream), then the levels [0, k) while it runs
+        (k, hook), buf = state.split, param.grad.view(-1)
+        _lib.call("emer_hashgrid_bwd_params_sliced_levels", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks), _ptr(buf), N, k, L, st)
+        hook(param, int(desc.offset[k]) * F, pc.numel())
+        _lib.call("emer_hashgrid_bwd_params_sliced_levels", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks), _ptr(buf), N, 0, k, st)
+    else:
+        # owner-computes LDS scatter: writes every entry once (no memset, no global atomics) -- straight into .grad ("direct"), [r5]
+        # added onto it in the write-out by a further evaluation of the same encoder in this step ("add"), or into a temporary
+        buf = param.grad.view(-1) if route in ("direct", "add") else torch.empty(pc.numel(), device=xc.device, dtype=torch.float32)
+        _lib.call("emer_hashgrid_bwd_params_sliced_add" if route == "add" else "emer_hashgrid_bwd_params_sliced", ctypes.byref(desc), _ptr(xc),
+                  _ptr(dlm), F, N * F, _ptr(masks), _ptr(buf), N, st)
+        if route == "temp_add":
+            param.grad.view(-1).add_(buf)
+        elif route == "sliced_autograd":
+            grad = buf
+    if route in ("direct", "direct_split"):
+        state.fresh = False
+    if grad is not None:
+        grad = grad.to(gdt).to(ctx.master_dtype)  # (half gradients of an odd feature count: summed in fp32, rounded once)
+        state.returning_through_autograd(ctx.param_obj)
+    state.complete(ctx.param_obj, ctx.last, grad is None)
+    return grad
 
 
 class _HashGridFn(torch.autograd.Function):
@@ -204,20 +259,8 @@ class _HashGridFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, params: Tensor, desc: GridDesc, grad_dtype):
         xc, pc = _f32c(x), params.detach().contiguous()
-        N, L, F = xc.shape[0], desc.n_levels, desc.n_features
-        gdt = grad_dtype or torch.float32
-        # the forward emits the slice masks of the owner-computes backward when it will be used
-        ctx.sliced = bool(ctx.needs_input_grad[1] and _fp32_accumulation(gdt, desc) and sliced_supported(desc))
-        if ctx.sliced:
-            lm, masks = hashgrid_fwd_raw(desc, xc, pc, level_major=True, want_masks=True)
-        else:
-            lm, masks = hashgrid_fwd_raw(desc, xc, pc, level_major=True), None
-        out = layout_transpose(lm, L, N, F, to_row_major=True)
-        ctx.desc, ctx.grad_dtype = desc, grad_dtype
-        ctx.param_obj = params
-        _count_table_eval(params)
-        ctx.save_for_backward(xc, pc, masks)
-        return out
+        lm, _ = _grid_forward(ctx, xc, pc, params, desc, grad_dtype)   # (no sink: its table gradient always returns through autograd)
+        return layout_transpose(lm, desc.n_levels, xc.shape[0], desc.n_features, to_row_major=True)
 
     @staticmethod
     def backward(ctx, dout: Tensor):
@@ -225,59 +268,17 @@ class _HashGridFn(torch.autograd.Function):
         desc = ctx.desc
         N, L, F = xc.shape[0], desc.n_levels, desc.n_features
         dx = dp = None
-        _before_table_grad(ctx.param_obj)
+        _enter_grid_backward(ctx, masks)
         with torch.cuda.device(xc.device):
             dlm = layout_transpose(_f32c(dout), L, N, F, to_row_major=False)
             st = _stream(xc)
             if ctx.needs_input_grad[1]:
-                gdt = ctx.grad_dtype or torch.float32
-                if masks is not None:
-                    # owner-computes LDS scatter: writes every entry once (no memset, no global atomics)
-                    grad = torch.empty(pc.numel(), device=xc.device, dtype=torch.float32)
-                    _lib.call("emer_hashgrid_bwd_params_sliced", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks),
-                              _ptr(grad), N, st)
-                else:  # tcnn-style global atomics: fp16-gradient mode, or tables too large for 32 LDS slices
-                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=torch.float32 if _fp32_accumulation(gdt, desc) else gdt)
-                    _lib.call("emer_hashgrid_bwd_params", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(grad),
-                              _dtype_tag(grad), N, st)
-                if grad.dtype != gdt:
-                    grad = grad.to(gdt)  # (half gradients of an odd feature count: summed in fp32, rounded once)
-                dp = _table_grad_via_autograd(ctx.param_obj, grad.to(pc.dtype) if grad.dtype != pc.dtype else grad)
+                dp = _table_gradient(ctx, desc, xc, dlm, masks, pc, st)
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(xc)
                 _lib.call("emer_hashgrid_bwd_input", ctypes.byref(desc), _ptr(xc), _ptr(pc), _dtype_tag(pc), _ptr(dlm), F,
                           N * F, _ptr(dx), N, st)
         return dx, dp, None, None
-
-
-def _count_table_eval(param) -> None:
-    """Data-parallel trainers hang ``_emer_before_table_grad`` on the table whose backward runs LAST in a step and
-    ``_emer_after_table_grad`` on the other tables of the main model.  If an encoder is evaluated more than once per step (warped
-    positions, chunked training), only the backward of its FIRST forward evaluation is the last one to run; the evaluations are
-    counted here so the callbacks fire exactly then (the trainer resets the count at the start of a step)."""
-    if getattr(param, "_emer_before_table_grad", None) is not None or getattr(param, "_emer_after_table_grad", None) is not None:
-        param._emer_pending_evals = getattr(param, "_emer_pending_evals", 0) + 1
-
-
-def _before_table_grad(param) -> bool:
-    """-> True when this is the last backward of ``param``'s encoder in the step (and a trainer asked to know)."""
-    cb, after = getattr(param, "_emer_before_table_grad", None), getattr(param, "_emer_after_table_grad", None)
-    if cb is None and after is None:
-        return False
-    left = getattr(param, "_emer_pending_evals", 1) - 1
-    param._emer_pending_evals = max(left, 0)
-    if left <= 0 and cb is not None:  # the last backward of this table in the step: everything upstream has its gradient enqueued by now
-        cb()
-    return left <= 0
-
-
-def _after_table_grad(param, last: bool, in_place: bool) -> None:
-    """The table's gradient of this step is complete IN the trainer's buffer (``in_place``: written or added there by this
-    backward, not handed to autograd's AccumulateGrad): a data-parallel trainer starts the table's collective now, behind the
-    backward kernels that follow."""
-    cb = getattr(param, "_emer_after_table_grad", None)
-    if cb is not None and last and in_place:
-        cb(param)
 
 
 class _HashGridLMFn(torch.autograd.Function):
@@ -286,9 +287,9 @@ class _HashGridLMFn(torch.autograd.Function):
 
     Gradient sink (``fused.grad_sinks()``, a trainer that owns its gradient buffers): the owner-computes backward writes
     every table entry exactly once, so it can write STRAIGHT into the parameter's ``.grad`` -- no 49 MB temporary, no
-    AccumulateGrad add, and the trainer does not zero the table's gradient beforehand (``params._emer_grad_fresh`` is set
-    by the trainer's zero_grad: the first backward of a step overwrites, later ones of the same step -- the flow
-    configs evaluate an encoder three times -- add).
+    AccumulateGrad add, and the trainer does not zero the table's gradient beforehand (its zero_grad marks the table's state
+    ``fresh``, table_grad.py: the first backward of a step overwrites, later ones of the same step -- the flow configs evaluate
+    an encoder three times -- add).  Which of the six routes a backward took: ``out.grad_fn.table_route``.
 
     ``table_dtype=torch.float16`` with an fp32 ``params``: half-precision tables the way BASELINE.md 2.2 / tcnn run them --
     the fp32 MASTER is cast to fp16 for this call (emer_cast_f32_f16), the encode and the input gradient read the fp16 copy
@@ -304,27 +305,12 @@ class _HashGridLMFn(torch.autograd.Function):
             with torch.cuda.device(pc.device):
                 _lib.call("emer_cast_f32_f16", _ptr(pc), _ptr(ph), pc.numel(), _stream(pc))
             pc = ph  # what the kernels read; `params` stays the fp32 master (gradient sink)
-        gdt = grad_dtype or torch.float32
-        ctx.sliced = bool(ctx.needs_input_grad[1] and _fp32_accumulation(gdt, desc) and sliced_supported(desc))
         k = min(int(skip_dx_rows), xc.shape[0])
-        jac = None
-        if GRID_JAC and ctx.needs_input_grad[0] and pc.dtype == torch.float32 and k < xc.shape[0] and _jac_fits(desc, xc.shape[0] - k):
-            res = hashgrid_fwd_raw(desc, xc, pc, level_major=True, want_masks=ctx.sliced, jac_row0=k)
-            lm, masks, jac = res if ctx.sliced else (res[0], None, res[1])
-        elif ctx.sliced:
-            lm, masks = hashgrid_fwd_raw(desc, xc, pc, level_major=True, want_masks=True)
-        else:
-            lm, masks = hashgrid_fwd_raw(desc, xc, pc, level_major=True), None
-        ctx.jac = jac   # (not through save_for_backward: never an input or output of the function, freed with the node)
-        ctx.desc, ctx.grad_dtype = desc, grad_dtype
-        ctx.skip_dx_rows = int(skip_dx_rows)
-        ctx.master_dtype = params.dtype
+        want_jac = GRID_JAC and ctx.needs_input_grad[0] and pc.dtype == torch.float32 and k < xc.shape[0] and _jac_fits(desc, xc.shape[0] - k)
+        # (the Jacobian not through save_for_backward: never an input or output of the function, freed with the node)
         from . import fused
-        sink = fused._sink(params) if (ctx.sliced and gdt == torch.float32) else None
-        ctx.param = params if (sink is not None and sink.is_contiguous() and sink.numel() == pc.numel()) else None
-        ctx.param_obj = params
-        _count_table_eval(params)
-        ctx.save_for_backward(xc, pc, masks)
+        lm, ctx.jac = _grid_forward(ctx, xc, pc, params, desc, grad_dtype, jac_row0=k if want_jac else None, sink_of=fused._sink)
+        ctx.skip_dx_rows = int(skip_dx_rows)
         return lm
 
     @staticmethod
@@ -333,51 +319,14 @@ class _HashGridLMFn(torch.autograd.Function):
         desc = ctx.desc
         N, L, F = xc.shape[0], desc.n_levels, desc.n_features
         dx = dp = None
-        last = _before_table_grad(ctx.param_obj)  # data-parallel trainer: early gradient bucket (fires on the table's last backward)
+        _enter_grid_backward(ctx, masks)
         with torch.cuda.device(xc.device):
             dlm = _f32c(dlm)
             if CHECK_FINITE:
                 _check_finite_grid_grad(dlm, desc)
             st = _stream(xc)
             if ctx.needs_input_grad[1]:
-                gdt = ctx.grad_dtype or torch.float32
-                if masks is not None:
-                    param = ctx.param
-                    direct = param is not None and getattr(param, "_emer_grad_fresh", False) and param.grad is not None
-                    # [r5] a further evaluation of the same encoder in this step adds to the table's buffer in the kernel's write-out
-                    add = (not direct) and param is not None and param.grad is not None and param.grad.is_contiguous()
-                    grad = param.grad.view(-1) if (direct or add) else torch.empty(pc.numel(), device=xc.device, dtype=torch.float32)
-                    # (the cut is taken only by the table's LAST backward of the step: an earlier one would start the collective of a range
-                    # that a later backward of the same table still adds to)
-                    split = getattr(ctx.param_obj, "_emer_table_split", None) if (direct and last) else None
-                    if split is not None and 0 < split[0] < L:
-                        # data-parallel trainer: the levels [k, L) first, then ITS hook (the collective of that contiguous range of the
-                        # table starts on the communication stream), then the levels [0, k) while it runs
-                        k, hook = split
-                        _lib.call("emer_hashgrid_bwd_params_sliced_levels", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks),
-                                  _ptr(grad), N, k, L, st)
-                        hook(param, int(desc.offset[k]) * F, pc.numel())
-                        _lib.call("emer_hashgrid_bwd_params_sliced_levels", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(masks),
-                                  _ptr(grad), N, 0, k, st)
-                    else:
-                        _lib.call("emer_hashgrid_bwd_params_sliced_add" if add else "emer_hashgrid_bwd_params_sliced", ctypes.byref(desc), _ptr(xc),
-                                  _ptr(dlm), F, N * F, _ptr(masks), _ptr(grad), N, st)
-                    if direct:
-                        param._emer_grad_fresh = False
-                        grad = None
-                    elif add:
-                        grad = None
-                    elif param is not None and param.grad is not None:
-                        param.grad.view(-1).add_(grad)  # a further evaluation of the same encoder in this step
-                        grad = None
-                else:
-                    grad = torch.zeros(pc.numel(), device=xc.device, dtype=torch.float32 if _fp32_accumulation(gdt, desc) else gdt)
-                    _lib.call("emer_hashgrid_bwd_params", ctypes.byref(desc), _ptr(xc), _ptr(dlm), F, N * F, _ptr(grad),
-                              _dtype_tag(grad), N, st)
-                if grad is not None and grad.dtype != gdt:
-                    grad = grad.to(gdt)  # (half gradients of an odd feature count: summed in fp32, rounded once)
-                dp = None if grad is None else _table_grad_via_autograd(ctx.param_obj, grad.to(ctx.master_dtype) if grad.dtype != ctx.master_dtype else grad)
-                _after_table_grad(ctx.param_obj, last, dp is None)
+                dp = _table_gradient(ctx, desc, xc, dlm, masks, pc, st)
             if ctx.needs_input_grad[0]:
                 k, D = min(ctx.skip_dx_rows, N), desc.n_dims
                 dx = torch.empty_like(xc)

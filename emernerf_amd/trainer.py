@@ -27,7 +27,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import Tensor
 
-from . import fused, ops, ray_jobs
+from . import fused, ops, ray_jobs, table_grad
 from .prop_net import PropNetEstimator, get_proposal_requires_grad_fn
 from .radiance_field import DensityField, RadianceField, build_density_field, build_radiance_field_from_cfg
 from .render_utils import render_rays
@@ -142,6 +142,9 @@ class FlatParams:
         names = {id(p): n for m in [m for mods in groups.values() for m in mods] for n, p in m.named_parameters()}
         self._table_offsets = [(p, o) for p, o in plist if names.get(id(p), "").endswith("tcnn_encoding.params")]
         self._tables = [p for p, _ in self._table_offsets]
+        # per table: (how its gradient reaches this buffer, step by step: table_grad.py; its range of the buffer -- a view made once:
+        # ``self.grads`` is never reassigned, the parameters' ``.grad`` views depend on that as well)
+        self._table_sinks = [(table_grad.of(p, create=True), self.grads[o:o + p.numel()]) for p, o in self._table_offsets]
         table_ids = {id(p) for p in self._tables}
         self._dense_ranges = []
         for p, o in plist:
@@ -161,17 +164,15 @@ class FlatParams:
         for p, o in self._plist:  # autograd may have replaced .grad; re-pin the views
             if p.grad is None or p.grad.data_ptr() != self.grads.data_ptr() + 4 * o:
                 p.grad = self.grads[o:o + p.numel()].view(p.shape)
-        for p in self._tables:
-            p._emer_grad_fresh = True
-            p._emer_pending_evals = 0   # (a forward without a backward -- an eval render between steps -- must not shift the count)
+        for state, _ in self._table_sinks:
+            state.begin_step()
 
     def finish_grads(self, group: str) -> None:
         """Tables of ``group`` that no backward wrote this step get their zero gradient now."""
         a, b = self.ranges[group]
-        for p, o in self._table_offsets:
-            if a <= o < b and getattr(p, "_emer_grad_fresh", False):
-                self.grads[o:o + p.numel()].zero_()
-                p._emer_grad_fresh = False
+        for (_, o), (state, view) in zip(self._table_offsets, self._table_sinks):
+            if a <= o < b:
+                state.take_stale(view)
 
 
 def capture_main_grid_positions(trainer: "Trainer", data: Dict[str, Tensor]) -> Tensor:
@@ -315,7 +316,7 @@ class Trainer:
         if self._dp_on:
             assert dist.is_initialized(), "data-parallel exchange needs an initialised torch.distributed process group"
             tab = self.model.xyz_encoder.tcnn_encoding.params
-            tab._emer_before_table_grad = self._launch_early_bucket
+            table_grad.of(tab).on_last_backward = self._launch_early_bucket
             # [r4] The exposed exchange of a step used to be the whole static table (48 MB at configs[1]) AFTER its backward, the
             # longest kernel of the step, with nothing left to hide it behind.  The owner-computes backward now runs as two launches
             # over a partition of the levels: the finest levels that fill one round of the resident owners first (cfg 2: levels
@@ -326,15 +327,13 @@ class Trainer:
                 desc = self.model.xyz_encoder.tcnn_encoding.desc
                 k = int(_os.environ.get("EMER_DP_SPLIT_LEVEL", "0")) or ops.sliced_split_level(desc)
                 if 0 < k < desc.n_levels and ops.sliced_supported(desc):
-                    tab._emer_table_split = (k, self._launch_table_bucket)
-            # the other tables of the main model (dynamic and flow xyzt grids): their backwards run BEFORE the static table's (their
-            # encoders come later in the forward), so each one's all-reduce starts when its last backward of the step has written
-            # it and runs behind the backward kernels that follow -- three serial collectives after the backward before [r4]
-            if self.dp_mode == "allreduce" and _os.environ.get("EMER_DP_SPLIT_TABLE", "1") != "0":
-                a, b = self.flat.ranges["main"]
+                    table_grad.of(tab).split = (k, self._launch_table_bucket)
+                # the other tables of the main model (dynamic and flow xyzt grids): their backwards run BEFORE the static table's (their
+                # encoders come later in the forward), so each one's all-reduce starts when its last backward of the step has written
+                # it and runs behind the backward kernels that follow -- three serial collectives after the backward before [r4]
                 for p, o in self.flat._table_offsets:
                     if a <= o < b and p is not tab:
-                        p._emer_after_table_grad = self._launch_whole_table_bucket
+                        table_grad.of(p).on_complete = self._launch_whole_table_bucket
         self.model.train(); self.estimator.train()
         for p in self.props:
             p.train()
@@ -503,7 +502,7 @@ class Trainer:
         self._table_ranges.append((a, b))
 
     def _launch_whole_table_bucket(self, param) -> None:
-        """Called by the last backward of a dynamic / flow table in a step, after it wrote the table's gradient (ops._after_table_grad)."""
+        """Called by the last backward of a dynamic / flow table in a step, after it wrote the table's gradient (TableGrad.on_complete)."""
         self._launch_table_bucket(param, 0, param.numel())
 
     def _launch_prop_bucket(self) -> None:
@@ -570,8 +569,6 @@ class Trainer:
             self.comm_events.append((ev0, ev1))
         self._early_done, self._early_work, self._prop_work = False, [], None
         self._table_work, self._table_ranges = [], []
-        if self._dp_on:
-            self.model.xyz_encoder.tcnn_encoding.params._emer_pending_evals = 0
 
     def _adam(self, group: str, lr: float):
         a, b = self.flat.ranges[group]

@@ -255,7 +255,7 @@ def _exchange_worker(rank, world, port, ret, dp_mode, early, table_cut, prop_gra
     g = torch.Generator().manual_seed(7 + rank)
     flat.grads.copy_(torch.randn(flat.numel, generator=g))
     for p in flat._tables:
-        p._emer_grad_fresh = False   # every table "was written" this step
+        T.table_grad.of(p).fresh = False   # every table "was written" this step
     mine = flat.grads.clone()
     tr = types.SimpleNamespace(flat=flat, world_size=world, dp_mode=dp_mode, dp_debug=False, comm_events=None, _dp_on=True, _hold_buckets=False,
                                _rs_emulate=True, _early_done=False, _early_work=[], _prop_work=None, _table_work=[], _table_ranges=[],

@@ -68,8 +68,10 @@ def _worker(rank, port, out_dir, kind, mode, dp_mode, debug):
         orig_early()
     tr._launch_prop_bucket = spy_prop
     tab = tr.model.xyz_encoder.tcnn_encoding.params
-    tab._emer_before_table_grad = spy_early
-    split = getattr(tab, "_emer_table_split", None)
+    from emernerf_amd import table_grad
+    state = table_grad.of(tab)
+    state.on_last_backward = spy_early
+    split = state.split
     calls["table"] = 0
     if dp_mode == "allreduce":
         assert split is not None, "all-reduce mode: the static table's backward must be split by level range"
@@ -82,19 +84,19 @@ def _worker(rank, port, out_dir, kind, mode, dp_mode, debug):
             orig_table(param, lo, hi)
             if not debug:
                 assert len(tr._table_work) == n_before + 1, "the first level range's all-reduce must be in flight before the second launch"
-        tab._emer_table_split = (k, spy_table)
+        state.split = (k, spy_table)
     else:
         assert split is None
     calls["xyzt"] = 0
     for p, _ in tr.flat._table_offsets:   # the dynamic / flow tables: their collectives start from their own last backward
-        orig_after = getattr(p, "_emer_after_table_grad", None)
+        orig_after = table_grad.of(p).on_complete
         if orig_after is not None:
             def spy_after(param, _orig=orig_after):
                 calls["xyzt"] += 1
                 n_before = len(tr._table_work) + len(tr._table_snapshots)
                 _orig(param)
                 assert len(tr._table_work) + len(tr._table_snapshots) == n_before + 1
-            p._emer_after_table_grad = spy_after
+            table_grad.of(p).on_complete = spy_after
     calls["all_reduce"] = 0
     orig_all_reduce = dist.all_reduce
 

@@ -211,6 +211,43 @@ def test_table_gradient_fallbacks_honour_the_unzeroed_grad_contract(hip_lib, mon
     assert float((g_ref[0][a:b] - g_ref[1][a:b]).abs().max()) <= 1e-5 * scale
 
 
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_tables_end_a_step_neither_fresh_nor_pending(hip_lib, use_graph):
+    """The state a step leaves on its tables (emernerf_amd/table_grad.py): no evaluation pending on any table, and no table of a
+    group the step trained still marked ``fresh`` -- its gradient was overwritten by a backward or zeroed by ``finish_grads``.
+    (The tables of a group the step did NOT train -- the idle proposal net always, the trained one on the steps without proposal
+    training -- keep the mark, as before the state objects: nothing wrote their gradient and nothing reads it.)  Three steps: without proposal training, with
+    it, with it again; under ``use_graph`` the first two capture a graph each and the third only replays one, so none of the
+    step's Python runs.  Then two backward passes on the same data without an optimizer step give the same gradient."""
+    from emernerf_amd import table_grad
+    tr, data = _make(use_graph)
+    tr.step_count = 0
+    assert len(tr.flat._tables) == 3 and all(getattr(p, "_emer_table", None) is not None for p in tr.flat._tables)
+    kinds = []
+    for _ in range(3):
+        n_graphs = len(tr._graphs)
+        out = tr.train_step(data)
+        kinds.append((out["prop_grad"], len(tr._graphs) > n_graphs))
+        trained = [tr.flat.ranges[g] for g in (("main", "prop") if out["prop_grad"] else ("main",))]
+        for p, o in tr.flat._table_offsets:
+            state = table_grad.of(p)
+            assert state.pending_evals == 0
+            if any(a <= o < b for a, b in trained):
+                assert state.fresh is False, f"step {len(kinds)}: the table at {o} is still marked fresh"
+            else:
+                assert state.fresh is True, f"step {len(kinds)}: the table at {o} of a group the step did not train lost its mark"
+    assert kinds == [(False, use_graph), (True, use_graph), (True, False)]
+    grads = []
+    for _ in range(2):
+        tr._forward_backward(data, False)
+        tr._exchange_grads(False)
+        grads.append(tr.flat.grads.clone())
+    a, b = tr.flat.ranges["main"]
+    scale = float(grads[0][a:b].abs().max())
+    assert scale > 0
+    assert float((grads[0][a:b] - grads[1][a:b]).abs().max()) <= 1e-5 * scale, "the second backward saw the first one's table gradients"
+
+
 def test_lr_schedule_ticks_twice_with_lidar_supervision(hip_lib):
     """scheduler.step() follows the pixel AND the lidar optimizer step in the reference (train_emernerf.py:745, :826)."""
     from emernerf_amd.trainer import synthetic_lidar_rays
@@ -251,17 +288,18 @@ def test_batched_xyzt_evaluations_equal_call_by_call(hip_lib, monkeypatch, kind)
 
 
 def test_table_split_is_taken_by_the_last_backward_only(hip_lib):
-    """The level cut of the data-parallel exchange (``_emer_table_split``) hands a range of the table's gradient to a collective while
+    """The level cut of the data-parallel exchange (``TableGrad.split``) hands a range of the table's gradient to a collective while
     the rest is still being computed, so it may only be taken by a backward after which nothing writes that range again: the table's
     LAST backward of the step, writing the table's buffer directly.  One evaluation per step: the cut is taken and the range is final
     when the hook runs.  Two evaluations (warped positions, chunked training): the first backward to run is not the last one and the
     last one ADDS to what the first wrote -- no cut, the whole table goes with the late bucket."""
-    from emernerf_amd import fused, ops
+    from emernerf_amd import fused, ops, table_grad
     from emernerf_amd.tcnn_modules import Encoding
     dev = torch.device("cuda:0")
     enc = Encoding(3, dict(otype="HashGrid", n_levels=16, n_features_per_level=2, log2_hashmap_size=19, base_resolution=16,
                            per_level_scale=1.3819)).to(dev)
     desc, tab = enc.desc, enc.params
+    state = table_grad.of(tab, create=True)
     with torch.no_grad():
         tab.copy_(torch.rand_like(tab) - 0.5)
     assert ops.sliced_supported(desc)
@@ -273,13 +311,13 @@ def test_table_split_is_taken_by_the_last_backward_only(hip_lib):
 
     def run(with_hooks, two):
         tab.grad = torch.full_like(tab, float("nan"))   # the first backward of a step overwrites (no zero fill)
-        tab._emer_grad_fresh, tab._emer_pending_evals = True, 0
+        state.begin_step()
         seen = []
         if with_hooks:
-            tab._emer_before_table_grad = lambda: seen.append(("before",))
-            tab._emer_table_split = (k, lambda p, lo, hi: seen.append(("split", tab.grad.view(-1)[lo:hi].clone(), lo, hi)))
+            state.on_last_backward = lambda: seen.append(("before",))
+            state.split = (k, lambda p, lo, hi: seen.append(("split", tab.grad.view(-1)[lo:hi].clone(), lo, hi)))
         else:
-            tab._emer_before_table_grad = tab._emer_table_split = None
+            state.on_last_backward = state.split = None
         with fused.grad_sinks(True):
             loss = (ops.hashgrid_encode_lm(xa, tab, desc) * da).sum()
             if two:
@@ -302,7 +340,7 @@ def test_table_split_is_taken_by_the_last_backward_only(hip_lib):
                 assert (lo, hi) == (int(desc.offset[k]) * 2, tab.numel())
                 assert float((at_hook - got[lo:hi]).abs().max()) == 0.0, "the level range was written after its collective would have started"
     finally:
-        tab._emer_before_table_grad = tab._emer_table_split = None
+        state.on_last_backward = state.split = None
 
 
 def test_default_timestep_registration_takes_the_fused_warp(hip_lib):

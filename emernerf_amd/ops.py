@@ -1608,7 +1608,7 @@ def depth_range(lo=4.0, hi=120.0, depth: Optional[Tensor] = None, opacity: Optio
     return float(np.minimum(lo_c, hi_c)), float(np.abs(hi_c - lo_c))
 
 
-def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool, lo=4.0, hi=120.0) -> Tensor:
+def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool, lo=4.0, hi=120.0, out: Optional[Tensor] = None) -> Tensor:
     """One merged 8-bit video frame, uint8 [rows * H, cams * W, 3], from device images (emer_compose_frame: ONE launch per
     ``FRAME_TILES_MAX`` tiles).  ``tiles`` is a list of ``(kind, row, col, src, opacity | None)``: ``src`` fills the cell
     (row, col) of the frame; ``kind`` is "colour3" (src [H, W, 3]: ``uint8(255 * clip(x, 0, 1))``), "grey1" (src [H, W] on three
@@ -1618,7 +1618,8 @@ def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool,
     colour is written as 0.  Sources may be views with a storage offset; anything that is not contiguous fp32 is copied.  Cells
     that no tile names are zero.  A pixel's bytes depend on its own inputs, the kind and the flag alone.  A bound of ``"auto"``
     is the weighted-percentile bound of the frame's ONE depth tile (``depth_range``); a launch has one range, so with any other
-    number of depth tiles ``"auto"`` raises.  ``None`` raises as it always has."""
+    number of depth tiles ``"auto"`` raises.  ``None`` raises as it always has.  ``out``: a contiguous uint8 device frame of that
+    shape to write into; the cells that no tile names are then left as they are (``five_view_frame``)."""
     auto = (_is_auto(lo) or _is_auto(hi)) and lo is not None and hi is not None
     if auto and sum(1 for t in tiles if t[0] == "depth") != 1:
         raise NotImplementedError('compose_frame: a bound of "auto" is a weighted percentile of one depth image and a launch has one '
@@ -1649,7 +1650,10 @@ def compose_frame(tiles, H: int, W: int, rows: int, cams: int, fp64_scale: bool,
         d, o = next(k for k, t in zip(keep, tiles) if t[0] == "depth")
         dmin, dabs = depth_range(lo, hi, d, o)
     shape = (rows * H, cams * W, 3)
-    out = (torch.empty if len(cells) == rows * cams else torch.zeros)(shape, dtype=torch.uint8, device=ref.device)
+    if out is None:
+        out = (torch.empty if len(cells) == rows * cams else torch.zeros)(shape, dtype=torch.uint8, device=ref.device)
+    else:
+        _check_frame(out, shape, ref.device, "compose_frame")
     rng = (ctypes.c_double * 2)(dmin, dabs)
     with torch.cuda.device(ref.device):
         table = _turbo8_on(ref.device)
@@ -1669,6 +1673,102 @@ def depth_colours(depth: Tensor, opacity: Tensor, lo=4.0, hi=120.0) -> Tensor:
         raise ValueError(f"depth_colours: expected a [H, W] depth, got {tuple(depth.shape)}")
     H, W = depth.shape
     return compose_frame([("depth", 0, 0, depth, opacity)], H, W, 1, 1, False, lo, hi)
+
+
+def _check_frame(out: Tensor, shape, device, what: str) -> None:
+    if not isinstance(out, Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what}: `out` is a contiguous uint8 frame of shape {tuple(shape)} on the tiles' device")
+
+
+# ------------------------------------------------------------------------------------ the five-view resize (cubic-spline zoom)
+_TURBO64: dict = {}
+
+
+def _turbo64_on(device) -> Tensor:
+    t = _TURBO64.get(device)
+    if t is None:
+        t = _TURBO64[device] = torch.from_numpy(turbo_table()).to(device).contiguous()
+    return t
+
+
+def five_view_rows(W: int) -> int:
+    """``int(W * 0.46)``: the rows that a resized outer view of a five-camera frame keeps (utils/visualization_tools.py:41)."""
+    return int(int(W) * 0.46)
+
+
+def _zoom_launch(tiles, H: int, W: int, h_out: int, rows: int, cams: int, fp64_scale: bool, lo, hi, frame: Tensor, values: Optional[Tensor]):
+    """emer_zoom_tiles on checked ``(kind, row, col, src, opacity | None)`` tiles: ONE launch per ``FRAME_TILES_MAX`` tiles."""
+    if not 2 <= h_out <= H:
+        raise ValueError(f"zoom: {h_out} output rows from images of {H} rows: the resized view keeps 2 <= h <= H rows "
+                         "(h = int(W * 0.46) in a five-view frame)")
+    dmin, dabs = depth_range(lo, hi)
+    arr, keep = (_FrameTile * len(tiles))(), []
+    for i, (kind, row, col, src, opacity) in enumerate(tiles):
+        if kind not in TILE_KINDS:
+            raise ValueError(f"zoom: tile {i}: kind should be one of {tuple(TILE_KINDS)}, not {kind!r}")
+        _check_cuda(src, opacity)
+        want = (H, W, 3) if kind == "colour3" else (H, W)
+        if tuple(src.shape) != want:
+            raise ValueError(f"zoom: tile {i} ({kind}): expected {want}, got {tuple(src.shape)}")
+        if kind == "depth" and (opacity is None or tuple(opacity.shape) != want):
+            raise ValueError(f"zoom: tile {i}: a depth tile needs an opacity of shape {want}")
+        if not (0 <= row < rows and 0 <= col < cams):
+            raise ValueError(f"zoom: tile {i}: cell ({row}, {col}) outside the {rows} x {cams} frame")
+        s, o = _f32c(src), (_f32c(opacity) if kind == "depth" else None)
+        keep.append((s, o))
+        arr[i] = _FrameTile(s.data_ptr(), None if o is None else o.data_ptr(), TILE_KINDS[kind], int(row), int(col), 0)
+    ref = keep[0][0]
+    rng = (ctypes.c_double * 2)(dmin, dabs)
+    with torch.cuda.device(ref.device):
+        table = _turbo64_on(ref.device)
+        for first in range(0, len(tiles), FRAME_TILES_MAX):
+            n = min(FRAME_TILES_MAX, len(tiles) - first)
+            part = ctypes.cast(ctypes.byref(arr, first * ctypes.sizeof(_FrameTile)), ctypes.c_void_p)
+            _lib.call("emer_zoom_tiles", part, n, H, W, h_out, rows, cams, 1 if fp64_scale else 0, ctypes.cast(rng, ctypes.c_void_p), _ptr(table),
+                      _ptr(frame), _ptr(None if values is None else values[first:first + n]), _stream(ref))
+
+
+def zoom_rows(x: Tensor, h_out: int, kind: str = "colour3", opacity: Optional[Tensor] = None, lo=4.0, hi=120.0) -> Tensor:
+    """The values of the reference's ``scipy.ndimage.zoom(img, [h_out / H, 1, 1])`` (order 3, mirror prefilter) of one tile, fp64
+    [h_out, W, 3], before the rounding to the image's type and the clip (emer_zoom_tiles, csrc/frames.hip): ``x`` is the tile's
+    source as ``compose_frame`` takes it -- [H, W, 3] for "colour3", [H, W] for "grey1", "one_minus_grey1" (``1 - x`` in fp32)
+    and "depth" (with ``opacity``; the zoom then reads the fp64 colours of ``turbo_table()``).  Only the y axis is computed: along
+    x and the channels the reference's zoom is the identity up to its fp64 noise.  ``ValueError`` unless 2 <= h_out <= H.  A
+    non-finite value spoils its own column and channel (the reference: the whole view)."""
+    H, W = int(x.shape[0]), int(x.shape[1])
+    h_out = int(h_out)
+    _check_cuda(x, opacity)
+    values = torch.empty((1, max(h_out, 0), W, 3), dtype=torch.float64, device=x.device)
+    frame = torch.empty((H, W, 3), dtype=torch.uint8, device=x.device)
+    _zoom_launch([(kind, 0, 0, x, opacity)], H, W, h_out, 1, 1, False, lo, hi, frame, values)
+    return values[0]
+
+
+def five_view_frame(tiles, H: int, W: int, rows: int, fp64_scale: bool, lo=4.0, hi=120.0) -> Tensor:
+    """``compose_frame`` for a frame of five views under the reference's ``resize_five_views``: the tiles of columns 1 to 3 are
+    composed as they are, the tiles of columns 0 and 4 become a black cell whose bottom ``five_view_rows(W)`` rows hold the
+    cubic-spline zoom of the view (``zoom_rows``), clipped and cut to 8 bits -- colour and mask tiles after rounding to fp32 and
+    by ``fp64_scale``, depth tiles in fp64 throughout.  ONE ``compose_frame`` launch and ONE zoom launch into the same frame
+    (per ``FRAME_TILES_MAX`` tiles).  ``ValueError`` when ``int(W * 0.46)`` exceeds H (where the reference fails) or is below 2."""
+    H, W, rows = int(H), int(W), int(rows)
+    if not tiles:
+        raise ValueError("five_view_frame: no tiles")
+    if any(not 0 <= t[2] < 5 for t in tiles):
+        raise ValueError("five_view_frame: a frame of five views has the columns 0 to 4")
+    outer = [t for t in tiles if t[2] in (0, 4)]
+    inner = [t for t in tiles if t[2] not in (0, 4)]
+    h = five_view_rows(W)
+    if outer and not 2 <= h <= H:
+        raise ValueError(f"five_view_frame: the outer views keep int({W} * 0.46) = {h} rows, which should lie in 2 .. H = {H}")
+    ref = tiles[0][3]
+    _check_cuda(ref)
+    cells = {(int(t[1]), int(t[2])) for t in tiles}
+    frame = (torch.empty if len(cells) == rows * 5 else torch.zeros)((rows * H, 5 * W, 3), dtype=torch.uint8, device=ref.device)
+    if inner:
+        compose_frame(inner, H, W, rows, 5, fp64_scale, lo, hi, out=frame)
+    if outer:
+        _zoom_launch(outer, H, W, h, rows, 5, fp64_scale, lo, hi, frame, None)
+    return frame
 
 
 # ------------------------------------------------------------------------------------ voxel lift (bit masks)

@@ -25,8 +25,9 @@ deterministic.
 depth colouring, the cut to 8 bits -- in ONE launch of csrc/frames.hip, so that with ``render(..., to_host=False)`` only
 3 bytes per frame pixel leave the GPU.  Out of scope here: the video encoding itself (imageio's, or the caller's writer),
 the weighted-percentile depth bounds inside a merged frame (the loop passes 4 / 120 as the reference's does; one image's own
-bounds are ``ops.depth_colours(depth, opacity, "auto", "auto")``) and ``resize_five_views`` (groups of five views raise unless
-they are tiled unresized).
+bounds are ``ops.depth_colours(depth, opacity, "auto", "auto")``).  The reference's ``resize_five_views`` -- the two outer views
+of a five-camera frame shrunk by a cubic-spline zoom -- is the second launch of such a frame and is asked for by name
+(``five_view_resize="zoom"``).
 """
 from __future__ import annotations
 
@@ -406,7 +407,7 @@ def _tile_image(x, kind: str, key: str, device) -> Tensor:
 
 
 def compose_video_frames(render_results: Dict[str, list], num_timestamps: int, keys: List[str], num_cams: int, separate: bool = False,
-                         five_view_resize: bool = True):
+                         five_view_resize=True):
     """The 8-bit frames of the reference's ``save_concatenated_videos`` / ``save_seperate_videos`` (video_utils.py:507-627),
     composed on the device: a generator of ``(i, frame)`` (``separate=False``: one merged frame per timestep, the keys' rows
     stacked in the order of ``keys``) or ``(key, i, frame)`` (``separate=True``: key by key, one row each), ``frame`` a host uint8
@@ -421,11 +422,19 @@ def compose_video_frames(render_results: Dict[str, list], num_timestamps: int, k
     builds a frame; only its 3 bytes per pixel leave the GPU, into one of two alternating pinned buffers, while the next frame
     is composed.
 
-    Deviations from the reference: a NaN colour is written as 0 (numpy leaves that cast undefined); a group of exactly five
-    images raises ``NotImplementedError`` -- the reference shrinks the two outer views with a cubic-spline zoom
-    (``resize_five_views``), which is not implemented -- unless ``five_view_resize=False``, which tiles the five views
-    UNRESIZED; images that are neither [H, W, 3] nor one of the single-channel cases, or whose sizes differ within a frame,
-    raise ``ValueError``."""
+    A group of exactly five images is what the reference's ``resize_five_views`` changes (utils/visualization_tools.py:36-49):
+    views 0 and 4 become black with ``scipy.ndimage.zoom(img, [h / H, 1, 1])``, ``h = int(W * 0.46)``, clipped to [0, 1], in
+    their bottom h rows.  ``five_view_resize="zoom"`` does that on the device (``ops.five_view_frame``: one more launch per
+    frame, still 3 bytes per pixel leaving the GPU); a depth row's resized views are fp64 images there and are scaled by 255 in
+    fp64 in the separate mode too; ``h > H`` (where the reference fails) and ``h < 2`` raise ``ValueError``.  The default,
+    ``True``, keeps raising ``NotImplementedError`` for five views -- the zoom is asked for by name, as ``lo="auto"`` is -- and
+    ``False`` tiles the five views UNRESIZED, which is not the reference's picture.
+
+    Deviations from the reference: a NaN colour is written as 0 (numpy leaves that cast undefined); a non-finite value in a
+    resized view spoils its own column and channel of that view (the reference: the whole view); images that are neither
+    [H, W, 3] nor one of the single-channel cases, or whose sizes differ within a frame, raise ``ValueError``."""
+    if five_view_resize not in (True, False, "zoom"):
+        raise ValueError(f'five_view_resize is True, False or "zoom", not {five_view_resize!r}')
     plan = _frame_plan(render_results, keys, separate)
     if not plan:
         if separate:
@@ -459,11 +468,15 @@ def compose_video_frames(render_results: Dict[str, list], num_timestamps: int, k
                 if tuple(t.shape[:2]) != (H, W) or (o is not None and tuple(o.shape) != (H, W)):
                     raise ValueError(f"{key}: an image of {tuple(t.shape[:2])} in a frame of {(H, W)} images")
                 tiles.append((kind, r, c, t, o))
-        if cams == 5 and five_view_resize:
+        if cams == 5 and five_view_resize and five_view_resize != "zoom":
             raise NotImplementedError("compose_video_frames: groups of five views are resized by the reference with a cubic-spline zoom "
-                                      "(resize_five_views), which is not implemented; pass five_view_resize=False to tile them unresized")
+                                      '(resize_five_views): pass five_view_resize="zoom" for it, or five_view_resize=False to tile them '
+                                      "unresized")
         fp64 = (not separate) and any(kind == "depth" for _, kind, _, _ in rows)
-        frame = ops.compose_frame(tiles, H, W, len(rows), cams, fp64)
+        if cams == 5 and five_view_resize == "zoom":
+            frame = ops.five_view_frame(tiles, H, W, len(rows), fp64)
+        else:
+            frame = ops.compose_frame(tiles, H, W, len(rows), cams, fp64)
         slot = n_frames & 1
         n_frames += 1
         buf = pinned.get(slot)
@@ -511,7 +524,7 @@ def _imageio():
 
 def save_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int, keys: List[str] = ["gt_rgbs", "rgbs", "depths"],
                 num_cams: int = 3, save_seperate_video: bool = False, save_images: bool = False, fps: int = 10, verbose: bool = True,
-                writer_factory=None, image_writer=None, five_view_resize: bool = True):
+                writer_factory=None, image_writer=None, five_view_resize=True):
     """video_utils.py:471-504 on ``compose_video_frames``: the reference's signature (spelling included) and return value.
     ``writer_factory(path, mode="I"[, fps=fps])`` returns an object with ``append_data(frame)`` and ``close()`` and
     ``image_writer(path, image)`` writes one image; by default they are ``imageio.get_writer`` / ``imageio.imwrite``, imported
@@ -528,7 +541,7 @@ def _open_writer(writer_factory, path: str, num_timestamps: int, fps: int):
 
 def save_concatenated_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int,
                              keys: List[str] = ["gt_rgbs", "rgbs", "depths"], num_cams: int = 3, save_images: bool = False, fps: int = 10,
-                             verbose: bool = True, writer_factory=None, image_writer=None, five_view_resize: bool = True):
+                             verbose: bool = True, writer_factory=None, image_writer=None, five_view_resize=True):
     """video_utils.py:507-565: one merged frame per timestep to one writer; returns ``{"concatenated_frame": frame}`` with the
     frame at ``num_timestamps // 2`` (frame 0 of a single timestep).  ``save_images`` is ignored here, as in the reference."""
     return_frame_id = 0 if num_timestamps == 1 else num_timestamps // 2
@@ -546,7 +559,7 @@ def save_concatenated_videos(render_results: Dict[str, list], save_pth: str, num
 
 def save_seperate_videos(render_results: Dict[str, list], save_pth: str, num_timestamps: int,
                          keys: List[str] = ["gt_rgbs", "rgbs", "depths"], num_cams: int = 3, fps: int = 10, verbose: bool = False,
-                         save_images: bool = False, writer_factory=None, image_writer=None, five_view_resize: bool = True):
+                         save_images: bool = False, writer_factory=None, image_writer=None, five_view_resize=True):
     """video_utils.py:568-627: one video per key at ``<save_pth>_<key>.mp4`` (or ``.png``); returns ``{key: frame}`` with each
     key's frame at ``num_timestamps // 2``.  ``save_images`` also writes every view of every frame to
     ``<save_pth>_<key>_<i * 3 + j>.png`` -- the reference's numbering, whatever ``num_cams`` is.  One deviation: no writer is

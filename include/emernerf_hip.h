@@ -931,6 +931,17 @@ typedef struct emer_frame_tile {
 int emer_compose_frame(const emer_frame_tile *tiles, int32_t n_tiles, int32_t H, int32_t W, int32_t rows, int32_t cams,
                        int32_t fp64_scale, const double *depth_range, const uint8_t *table, uint8_t *out, void *stream);
 
+/* The five-view resize (utils/visualization_tools.py:36-49): ONE launch turns every listed tile into the reference's resized
+ * view -- black, with scipy.ndimage.zoom(img, [h_out / H, 1, 1]) (cubic spline, mirror prefilter; the y axis only, the others
+ * being the identity) in the bottom h_out rows -- and writes its cell of the frame, black rows included; other cells are left
+ * as they are.  2 <= h_out <= H.  A colour or mask tile is zoomed in fp64, rounded to fp32, clipped and scaled by the
+ * fp64_scale rule; a depth tile is the fp64 colour of `table64` (256 x 3 doubles on the device; black for a NaN position)
+ * before the zoom, stays fp64, is clipped and scaled in fp64.  values_out (or null): the fp64 values before rounding and clip,
+ * [n_tiles][h_out][W][3].  A non-finite source value spoils its own column and channel, nothing else. */
+int emer_zoom_tiles(const emer_frame_tile *tiles, int32_t n_tiles, int32_t H, int32_t W, int32_t h_out, int32_t rows, int32_t cams,
+                    int32_t fp64_scale, const double *depth_range, const double *table64, uint8_t *frame_out, double *values_out,
+                    void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Order statistics (csrc/select.hip): the k-th smallest value, torch.quantile's linear rule and the weighted percentile of
  * utils/visualization_tools.py:68-76 over ONE fp32 device array of n rows, by an exact radix select -- no sort, no size limit

@@ -562,6 +562,7 @@ class RgbRider:
         self.hray, self.S, self.params, self.keep = hray, int(samples_per_ray), tuple(params), bool(keep)
         self.geo_ptr = None
         self.rb = self.a1 = self.a2 = self.out = None   # rb: the per-ray pre-activations [R, 128] of layers 0 | 1
+        self.geo = self.versions = None                 # while parked: the geometry features and _versions of the query's tensors
 
     def usable(self, L: int, F: int, N: int, n_out: int) -> bool:
         w0, _, w1, _, w2, _ = self.params
@@ -574,7 +575,15 @@ class RgbRider:
 _RIDERS: dict = {}   # data_ptr of a neck's geometry features -> the rider whose rgb results were computed with them
 
 
+def _versions(geo: Tensor, hray: Tensor, params) -> tuple:
+    """Version counters of a colour query's tensors: an in-place write through torch between park and pick-up changes one of them (a write
+    through ``.data`` or by a kernel on the raw pointer does not: after those, clear_riders())."""
+    return (geo._version, hray._version) + tuple(p._version for p in params)
+
+
 def clear_riders() -> None:
+    for r in _RIDERS.values():
+        r.geo = None
     _RIDERS.clear()
     ray_jobs.clear_fronts()
 
@@ -671,6 +680,9 @@ def _field_fwd(enc: Tensor, W0, B0, W1, B1, rider: RgbRider):
     _launch("emer_field_fwd", enc, _p(enc), L, F, R, rider.S, _p(W0), _p(B0), _p(W1), _p(B1), _p(rb), _p(rb[:, 64:]), 128, Kh,
             _p(RW0), _p(RW1), _p(RW2), _p(RB2), _p(geo), _p(dens), _p(a1), _p(a2), _p(out))
     rider.geo_ptr, rider.a1, rider.a2, rider.out, rider.rb = geo.data_ptr(), a1, a2, out, rb
+    # what rgb_head needs to recognise these tensors, unchanged (the rule of ray_jobs.front_rb): their version counters now, and geo itself --
+    # while the entry is parked its storage cannot be freed, so no other tensor can appear at its address
+    rider.geo, rider.versions = geo, _versions(geo, rider.hray, rider.params)
     _RIDERS[geo.data_ptr()] = rider
     return geo, dens
 
@@ -878,10 +890,12 @@ def rgb_head(hray: Tensor, geo: Tensor, samples_per_ray: int, w0, b0, w1, b1, w2
         # too wide for one chain launch: the concatenated rows, layer by layer on emer_linear_*
         return _skip3_layers(torch.cat([hray.repeat_interleave(samples_per_ray, dim=0), geo], dim=-1), w0, b0, w1, b1, w2, b2, ACT_SIGMOID)
     pre = _RIDERS.pop(geo.data_ptr(), None)
-    if pre is not None:  # the same query, tensor for tensor, that rode along in the neck's launch?
+    if pre is not None:  # the same query, tensor for tensor and unchanged since, that rode along in the neck's launch?
         same = (pre.S == samples_per_ray and pre.hray.data_ptr() == hray.data_ptr() and pre.hray.shape == hray.shape
                 and geo.dim() == 2 and geo.shape[1] == 64 and geo.stride(0) == 64
-                and all(a is b for a, b in zip(pre.params, (w0, b0, w1, b1, w2, b2))))
+                and all(a is b for a, b in zip(pre.params, (w0, b0, w1, b1, w2, b2)))
+                and pre.versions == _versions(geo, hray, pre.params))
+        pre.geo = None   # no longer parked: the features live as long as their users hold them
         pre = pre if same else None
     rb_front = ray_jobs.front_rb(hray, (w0, b0, w1, b1)) if pre is None else None
     return _RgbHeadFn.apply(*_ng(hray, geo, samples_per_ray, w0, b0, w1, b1, w2, b2), pre, rb_front)

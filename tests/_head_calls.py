@@ -1,7 +1,8 @@
 """The forward and data-gradient entry points of csrc/mlp_fused.hip called directly (emer_neck_fwd / _bwd, emer_rgb_head_fwd / _bwd,
 emer_field_fwd, emer_rmlp_fwd / _bwd) on seeded CPU-generated inputs, with any optional pointer null: emernerf_amd.fused passes the
 combinations the training step needs, so only direct calls reach the others.  Output buffers start at 7.5, so a store that should not
-happen shows.  Shared by tests/test_fused_gpu.py and tools/head_entry_digests.py; `call` is emernerf_amd._lib.call or a stand-in with
+happen shows; with `guard` they are followed by sentinel rows, so a store past the end shows too.  Shared by tests/test_fused_gpu.py,
+tests/test_field_exact_gpu.py (which supplies its own arrays to rgb_case) and tools/head_entry_digests.py; `call` is emernerf_amd._lib.call or a stand-in with
 its signature (the tool times two builds of the library in one process), `o` the output buffers of an earlier call to be used again."""
 import torch
 
@@ -19,8 +20,25 @@ def _rnd(g, *shape, k=1.0):
     return (torch.randn(*shape, generator=g) * k).to(DEV)
 
 
-def buf(*shape):
-    return torch.full(shape, 7.5, device=DEV, dtype=torch.float32)
+GUARD = -3.25   # the fill of the sentinel rows
+
+
+def buf(*shape, guard=0):
+    """An output buffer filled with 7.5; guard > 0: the first rows of a taller allocation whose `guard` further rows hold GUARD."""
+    if not guard:
+        return torch.full(shape, 7.5, device=DEV, dtype=torch.float32)
+    full = torch.full((shape[0] + guard,) + tuple(shape[1:]), 7.5, device=DEV, dtype=torch.float32)
+    full[shape[0]:] = GUARD
+    return full[:shape[0]]
+
+
+def guard_rows(t):
+    """The sentinel rows behind a buffer made by buf(..., guard=n)."""
+    return t._base[t.shape[0]:]
+
+
+def _dev(x):
+    return torch.as_tensor(x, dtype=torch.float32).to(DEV).contiguous()
 
 
 def _pick(tensors, null):
@@ -58,33 +76,67 @@ def neck_bwd(c, fwd, null=(), call=_lib.call, o=None):
 
 
 # ------------------------------------------------------------------------------------------------ rgb head, field forward
-def rgb_case(R, S, Kh=49, L=0, F=0):
-    """The rgb head on R rays of S samples; with L, F also the neck in front of it (emer_field_fwd's input)."""
-    g, N = _gen(R, S, Kh, L, F), R * S
-    c = dict(R=R, S=S, Kh=Kh, N=N, geo=_rnd(g, N, 64), rb=_rnd(g, R, 128, k=0.5), w0=_rnd(g, 64, Kh + 64, k=0.1), w1=_rnd(g, 64, 128 + Kh, k=0.1),
-             w2=_rnd(g, 3, 64, k=0.125), b2=_rnd(g, 3, k=0.1), dout=_rnd(g, N, 3))
+RB_JUNK = 977.0    # the fill of the pad columns of rb when ld_rb > 128
+W_PAD_ROWS = 2     # rows of junk behind the head's w0 / w1 with pad_w (a view cut at a wrong column offset then stays inside the allocation)
+
+
+def rgb_case(R, S, Kh=49, L=0, F=0, ld_rb=128, arrays=None, pad_w=False):
+    """The rgb head on R rays of S samples; with L, F also the neck in front of it (emer_field_fwd's input).
+
+    ld_rb: leading dimension of rb [R][ld_rb] = [rb0 | rb1 | pad columns holding RB_JUNK].  arrays: caller-supplied values (numpy or
+    torch, any of geo, rb0, rb1 [R][64], w0, w1, w2, b2, enc, nw0, nb0, nw1, nb1) that replace the seeded ones; what is supplied is not
+    drawn, so the other seeded tensors then differ from those of a call without arrays.  pad_w: w0 / w1 are the first 64 rows of
+    matrices with W_PAD_ROWS more rows of junk."""
+    g, N, given = _gen(R, S, Kh, L, F), R * S, dict(arrays or {})
+    assert ld_rb >= 128 and ld_rb % 4 == 0
+
+    def pick(name, *shape, k=1.0):
+        return _dev(given.pop(name)) if name in given else _rnd(g, *shape, k=k)
+
+    def tall(w):
+        return torch.cat([w, torch.full((W_PAD_ROWS, w.shape[1]), 61.0, device=DEV)])[:64] if pad_w else w
+
+    geo = pick("geo", N, 64)
+    if "rb0" in given or "rb1" in given:
+        rb = torch.cat([_dev(given.pop("rb0")), _dev(given.pop("rb1"))], 1)
+    else:
+        rb = _rnd(g, R, 128, k=0.5)
+    assert rb.shape == (R, 128)
+    if ld_rb > 128:
+        rb = torch.cat([rb, torch.full((R, ld_rb - 128), RB_JUNK, device=DEV)], 1)
+    c = dict(R=R, S=S, Kh=Kh, N=N, ld_rb=ld_rb, geo=geo, rb=rb, w0=tall(pick("w0", 64, Kh + 64, k=0.1)), w1=tall(pick("w1", 64, 128 + Kh, k=0.1)),
+             w2=pick("w2", 3, 64, k=0.125), b2=pick("b2", 3, k=0.1), dout=_rnd(g, N, 3))
     if L:
         K0 = L * F
-        c.update(L=L, F=F, enc=_rnd(g, L, N, F, k=0.5), nw0=_rnd(g, 64, K0, k=K0 ** -0.5), nb0=_rnd(g, 64, k=0.1), nw1=_rnd(g, 64, 64, k=0.125),
-                 nb1=_rnd(g, 64, k=0.1))
+        c.update(L=L, F=F, enc=pick("enc", L, N, F, k=0.5), nw0=pick("nw0", 64, K0, k=K0 ** -0.5), nb0=pick("nb0", 64, k=0.1),
+                 nw1=pick("nw1", 64, 64, k=0.125), nb1=pick("nb1", 64, k=0.1))
+        assert c["enc"].shape == (L, N, F) and c["nw0"].shape == (64, K0)
+    assert not given, f"unknown arrays: {sorted(given)}"
+    assert c["w0"].shape == (64, Kh + 64) and c["w1"].shape == (64, 128 + Kh) and c["w0"].is_contiguous() and c["w1"].is_contiguous()
     return c
 
 
-def rgb_head_fwd(c, null=(), geo=None, call=_lib.call, o=None):
-    """Optional: a2, or a1 and a2."""
+def neck_of(c):
+    """The neck in front of the rgb head of rgb_case(..., L, F) as a case of neck_fwd (n_out = 64)."""
+    return dict(L=c["L"], F=c["F"], n_out=64, N=c["N"], enc=c["enc"], w0=c["nw0"], b0=c["nb0"], w1=c["nw1"], b1=c["nb1"])
+
+
+def rgb_head_fwd(c, null=(), geo=None, call=_lib.call, o=None, guard=0):
+    """Optional: a2, or a1 and a2.  guard: sentinel rows behind every output buffer (buf)."""
     geo = c["geo"] if geo is None else geo
-    o = o or _pick(dict(a1=buf(c["N"], 64), a2=buf(c["N"], 64), out=buf(c["N"], 3)), null)
-    call("emer_rgb_head_fwd", _ptr(geo), 64, _ptr(c["rb"]), _ptr(c["rb"][:, 64:]), 128, c["R"], c["S"], c["Kh"], _ptr(c["w0"]), _ptr(c["w1"]),
-         _ptr(c["w2"]), _ptr(c["b2"]), _ptr(o["a1"]), _ptr(o["a2"]), _ptr(o["out"]), _stream(geo))
+    o = o or _pick(dict(a1=buf(c["N"], 64, guard=guard), a2=buf(c["N"], 64, guard=guard), out=buf(c["N"], 3, guard=guard)), null)
+    call("emer_rgb_head_fwd", _ptr(geo), 64, _ptr(c["rb"]), _ptr(c["rb"][:, 64:]), c.get("ld_rb", 128), c["R"], c["S"], c["Kh"], _ptr(c["w0"]),
+         _ptr(c["w1"]), _ptr(c["w2"]), _ptr(c["b2"]), _ptr(o["a1"]), _ptr(o["a2"]), _ptr(o["out"]), _stream(geo))
     return o
 
 
-def field_fwd(c, null=(), call=_lib.call, o=None):
-    """Optional: a2, or a1 and a2."""
+def field_fwd(c, null=(), call=_lib.call, o=None, guard=0):
+    """Optional: a2, or a1 and a2.  guard: sentinel rows behind every output buffer (buf)."""
     N = c["N"]
-    o = o or _pick(dict(geo=buf(N, 64), dens=buf(N), a1=buf(N, 64), a2=buf(N, 64), out=buf(N, 3)), null)
+    o = o or _pick(dict(geo=buf(N, 64, guard=guard), dens=buf(N, guard=guard), a1=buf(N, 64, guard=guard), a2=buf(N, 64, guard=guard),
+                        out=buf(N, 3, guard=guard)), null)
     call("emer_field_fwd", _ptr(c["enc"]), c["L"], c["F"], c["R"], c["S"], _ptr(c["nw0"]), _ptr(c["nb0"]), _ptr(c["nw1"]), _ptr(c["nb1"]),
-         _ptr(c["rb"]), _ptr(c["rb"][:, 64:]), 128, c["Kh"], _ptr(c["w0"]), _ptr(c["w1"]), _ptr(c["w2"]), _ptr(c["b2"]), _ptr(o["geo"]),
+         _ptr(c["rb"]), _ptr(c["rb"][:, 64:]), c.get("ld_rb", 128), c["Kh"], _ptr(c["w0"]), _ptr(c["w1"]), _ptr(c["w2"]), _ptr(c["b2"]), _ptr(o["geo"]),
          _ptr(o["dens"]), _ptr(o["a1"]), _ptr(o["a2"]), _ptr(o["out"]), _stream(c["enc"]))
     return o
 

@@ -469,6 +469,65 @@ def test_field_forward_rides_along(hip_lib, L, Fe, R, S):
     assert rgb.data_ptr() != rider.out.data_ptr() and torch.equal(rgb, rider.out)
 
 
+@pytest.mark.parametrize("what", ["geo", "hray", "param", "param_data", "geo_realloc"])
+def test_rider_results_are_not_picked_up_for_changed_tensors(hip_lib, what):
+    """After fused.neck(..., rider=) parked the colours of (hray, geo, head parameters), fused.rgb_head must return what a call with no
+    rider anywhere returns for the tensors it is GIVEN: an in-place change of geo, of hray or of a head parameter between the two calls,
+    or another tensor at geo's address, must not be answered with the parked colours of the old values.
+
+    "param": p.add_() under no_grad bumps p._version, so the change is seen.  "param_data": p.data is a tensor with a version counter
+    of its own, p.data.add_() leaves p._version where it was -- like a kernel writing through the raw pointer, this is invisible to
+    the pick-up, and all that can be asserted is that fact (such writers call fused.clear_riders(), as RadianceField.forward does).
+    "geo_realloc": skipped when the allocator does not hand geo's address out again -- which it cannot while the parked entry
+    holds geo."""
+    from emernerf_amd import fused
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(77)
+    L, Fe, R, S, H, Kh = 10, 4, 7, 16, 64, 49
+    N = R * S
+    enc = (torch.randn(L, N, Fe, generator=g) * 0.5).to(dev)
+    pn = [w.to(dev) for w in (torch.randn(H, L * Fe, generator=g) / (L * Fe) ** 0.5, torch.randn(H, generator=g) * 0.1,
+                              torch.randn(H, H, generator=g) / 8, torch.randn(H, generator=g) * 0.1)]
+    ph = [w.to(dev) for w in (torch.randn(H, Kh + H, generator=g) / 10, torch.randn(H, generator=g) / 10, torch.randn(H, H + Kh + H, generator=g) / 12,
+                              torch.randn(H, generator=g) / 10, torch.randn(3, H, generator=g) / 8, torch.randn(3, generator=g) / 10)]
+    hray = torch.randn(R, Kh, generator=g).to(dev)
+    fused.clear_riders()
+    rider = fused.RgbRider(hray, S, ph, False)
+    with torch.no_grad():
+        geo, _, _ = fused.neck(enc, *pn, rider=rider)
+        assert rider.out is not None, "the rider was not taken"
+        parked = rider.out.clone()
+        if what == "geo":
+            geo.mul_(2.0)
+        elif what == "hray":
+            hray.mul_(2.0)
+        elif what == "param":
+            v = ph[2]._version
+            ph[2].add_(0.25)
+            assert ph[2]._version > v
+        elif what == "param_data":
+            v = ph[2]._version
+            ph[2].data.add_(0.25)
+            assert ph[2]._version == v, "p.data.add_ bumps p._version in this torch: assert the fresh result here as for 'param'"
+            return
+        else:
+            ptr, geo = geo.data_ptr(), None
+            held = []
+            for _ in range(4):
+                held.append(torch.randn(N, 64, generator=g).to(dev))
+                if held[-1].data_ptr() == ptr:
+                    geo = held[-1]
+                    break
+            if geo is None:
+                pytest.skip("the allocator did not hand the address of the parked geometry features to another [N, 64] tensor")
+        got = fused.rgb_head(hray, geo, S, *ph)
+        assert got.data_ptr() != rider.out.data_ptr(), "the parked colours of the old values were returned"
+        fused.clear_riders()
+        want = fused.rgb_head(hray, geo, S, *ph)
+    assert torch.equal(got, want)
+    assert not torch.equal(want, parked), "test broken: the change does not reach the colours"
+
+
 def test_hidden_stores_change_nothing_else(hip_lib):
     """The forward kernels share their stages between the entry points whether or not the hidden activations are stored (h1 of the
     neck, h1 / h2 of the plain heads, a1 / a2 of the rgb head: null when no backward will read them).  Through the C entry points at 33

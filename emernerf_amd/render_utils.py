@@ -32,6 +32,17 @@ def render_weights_opacity_depth_from_density(t_starts: Tensor, t_ends: Tensor, 
     return weights, opacities, depths
 
 
+def _extras(results: Dict[str, Tensor], weights: Tensor, trans: Tensor, t_vals: Tensor, t_dist: Tensor) -> Dict[str, Tensor]:
+    """The ``extras`` every render starts from (:84-85, 262-277): the scan's per-sample outputs and the field's four flow entries.  The
+    flow entries must be handed on as the SAME tensor objects, untouched (no reshape, slice or copy): one of them carries the flow
+    pair of the batched flow branch as an attribute (radiance_field.attach_flow_pair / flow_pair)."""
+    extras = {"weights": weights, "trans": trans, "t_vals": t_vals, "t_dist": t_dist}
+    for k in ["forward_flow", "backward_flow", "forward_pred_backward_flow", "backward_pred_forward_flow"]:
+        if k in results:
+            extras[k] = results[k]
+    return extras
+
+
 def rendering(t_starts: Tensor, t_ends: Tensor, query_fn: Optional[Callable] = None,
               return_decomposition: bool = False) -> Dict[str, Tensor]:
     """render_utils.py:48-287."""
@@ -45,10 +56,7 @@ def rendering(t_starts: Tensor, t_ends: Tensor, query_fn: Optional[Callable] = N
         rgb = results.get("rgb")
         weights, trans, t_vals, t_dist, opacities, depths, median_depth, rgb_out = ops.composite_rgb(
             t_starts, t_ends, density, rgb, results.get("rgb_sky") if rgb is not None else None)
-        extras = {"weights": weights, "trans": trans, "t_vals": t_vals, "t_dist": t_dist}
-        for k in ["forward_flow", "backward_flow", "forward_pred_backward_flow", "backward_pred_forward_flow"]:
-            if k in results:
-                extras[k] = results[k]
+        extras = _extras(results, weights, trans, t_vals, t_dist)
         results_dict = {"density": density, "depth": depths, "opacity": opacities, "median_depth": median_depth}
         if rgb_out is not None:
             results_dict["rgb"] = rgb_out
@@ -57,10 +65,7 @@ def rendering(t_starts: Tensor, t_ends: Tensor, query_fn: Optional[Callable] = N
     # one scan kernel: weights, transmittance, the per-ray sums behind opacity / depth / median depth (:102-122) and the
     # t_vals / t_dist extras (:84-85)
     weights, trans, _, _, stats, t_vals, t_dist = ops.render_weights(t_starts, t_ends, density, want_t=True)
-    extras = {"weights": weights, "trans": trans, "t_vals": t_vals, "t_dist": t_dist}
-    for k in ["forward_flow", "backward_flow", "forward_pred_backward_flow", "backward_pred_forward_flow"]:
-        if k in results:
-            extras[k] = results[k]
+    extras = _extras(results, weights, trans, t_vals, t_dist)
     results_dict = {"density": density}
 
     if "static_density" in results and "dynamic_density" in results:  # :125-155

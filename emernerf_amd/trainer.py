@@ -29,7 +29,7 @@ from torch import Tensor
 
 from . import fused, ops, ray_jobs, table_grad
 from .prop_net import PropNetEstimator, get_proposal_requires_grad_fn
-from .radiance_field import DensityField, RadianceField, build_density_field, build_radiance_field_from_cfg
+from .radiance_field import DensityField, RadianceField, build_density_field, build_radiance_field_from_cfg, flow_pair
 from .render_utils import render_rays
 
 
@@ -396,7 +396,7 @@ class Trainer:
         ex = results["extras"]
         flows = "forward_flow" in ex
         feat = "dino_feat" in results and "features" in data
-        pair = getattr(ex["forward_pred_backward_flow"], "_emer_flow_pair", None) if flows else None
+        pair = flow_pair(ex) if flows else None
         if pair is not None:   # batched flow branch: the cycle term from the flow MLP's two outputs, unsliced
             return ops.reg_losses(base, dynamic_density=ex.get("dynamic_density"), shadow_ratio=results.get("shadow_ratio"),
                                   feat=results["dino_feat"] if feat else None, feat_gt=data["features"] if feat else None,
